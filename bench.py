@@ -23,13 +23,25 @@ launcher (an explicit --gpus that disagrees is an error).
     --config c5   configs[4]: RN50 FairLoRA r=8, gender (2 groups), bs 32; the round
                   boundary also averages the BatchNorm buffers (second all-reduce)
 `value` of c4 / c5 is in that workload's own unit (volumes/sec, images/sec); the
-driver's line is c2.  The default c2 run reports c4 and c5 under `secondary`
+driver's line is c2.  With --full the c2 run reports c4 and c5 under `secondary`
 (child processes, each with its own `roofline`).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run sets
+up, warms up, times the K steps and prints that line; everything else it can
+measure comes with --full (each part still switched off by its --no-* flag):
   roofline      achieved TFLOP/s of the dominant kernel (the MFMA GEMM), timed
                 per launch with HIP events in a second pass over the same K steps
+  engine_only   the bare engine loop (forward_backward + sgd_step) over K more steps
+  trainer       GLP_OT_SVLoRA.train() over one 32-batch client-round, three reporting settings
+  secondary     configs[3] / configs[4] (c2 only, child processes)
   cpu_baseline  the oracle (CPU restatement of the reference) timed on the host
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step left
+                         to its caller (loss, logits, prob, the updated trainable
+                         parameters, their gradients and momentum; RN50 also its
+                         BatchNorm buffers) as DIR/<name>.npy in float32.  The inputs
+                         are seeded, so two builds run with the same arguments can be
+                         compared array for array.
 """
 from __future__ import annotations
 
@@ -45,8 +57,11 @@ if ROOT not in sys.path:
 
 # The engine runs three HIP streams (vision chain, text tower, LoRA-gradient reductions) and RCCL adds its
 # own; with ROCm's default of 4 hardware queues they get multiplexed and the overlap is lost (measured:
-# 9.4 vs 6.9 ms/step once a communicator exists).  Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# 9.4 vs 6.9 ms/step once a communicator exists).  Must be set before the HIP runtime initialises.  A smaller value
+# already in the environment (HIP's default of 4, spelled out by some launch environments) is raised to 8 as well:
+# with 4 queues the world-1 RCCL line ran at 6.06 against 4.55 ms/step for the same steps without a communicator.
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 8:
+    os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 import socket
 import subprocess
@@ -84,7 +99,16 @@ def parse():
                          "that are comparable with roofline.avg_launch_us")
     ap.add_argument("--launch", default="replay", choices=["replay", "eager", "graph"],
                     help="replay: recorded launch plan (default); eager: Python per launch; graph: one hipGraph per step")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, engine_only, trainer, secondary and cpu_baseline (each still off with its "
+                         "--no-* flag); without it the run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logits, prob, trainable parameters, gradients, momentum) "
+                         "to DIR/<name>.npy in float32")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_roofline = args.no_trainer = args.no_secondary = args.no_cpu_baseline = True
+    return args
 
 
 class GemmTimer:
@@ -312,7 +336,7 @@ def secondary_configs():
         try:
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--gpus", "1", "--steps", "10",
-                                "--warmup", "3", "--no-cpu-baseline", "--no-secondary", "--no-trainer", "--dtype", dt],
+                                "--warmup", "3", "--full", "--no-cpu-baseline", "--no-secondary", "--no-trainer", "--dtype", dt],
                                capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if line:
@@ -385,6 +409,26 @@ class Workload:
         self.attrs = batch["attrs"].to(dev)                    # [B, n_attr]: the trainer's batch format
         self.label = batch["label"].to(dev)
         self.has_buf = hasattr(self.eng, "buffers_flat")       # RN50: BatchNorm running statistics
+
+
+DUMP_MAX_ELEMS = 2 ** 21         # per array: 8 MB of float32, so that a dump stays far below 64 MB
+
+
+def dump_outputs(eng, n, out_dir):
+    """What the last timed step leaves to its caller, as float32 .npy files: loss, logits and prob of its batch (n
+    samples), the trainable parameters after its SGD update, their gradients and momentum, and RN50's BatchNorm
+    buffers.  An array larger than DUMP_MAX_ELEMS is written as a fixed sample (seeded indices, sorted)."""
+    import numpy as np
+    arrays = {"loss": eng.loss, "logits": eng.logits[:n], "prob": eng.prob[:n], "trainable": eng.params.flat,
+              "grad": eng.params.grad, "momentum": eng.params.momentum}
+    if hasattr(eng, "buffers_flat"):
+        arrays["bn_buffers"] = eng.buffers_flat()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -507,8 +551,10 @@ def main():
         dt = float(t)
     finite = int(eng.finite)
     loss = float(eng.loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, wl.label.shape[0], args.dump_outputs)
     engine_only = None
-    if trainer_step:
+    if trainer_step and args.full:
         # the bare engine loop on the same engine (earlier rounds' headline): K steps, same bracket, max over ranks
         tr.check_finite()
         torch.cuda.synchronize()

@@ -21,7 +21,8 @@ def last_json(out: str) -> dict:
 
 
 def test_single_gpu_line_has_roofline_and_cpu_baseline_fields():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--no-secondary"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = last_json(r.stdout)
@@ -41,6 +42,24 @@ def test_single_gpu_line_has_roofline_and_cpu_baseline_fields():
     for mode in ("default", "every_32", "sync_per_step"):
         assert t[mode]["images_per_sec_per_client"] > 100 and t[mode]["ms_per_step"] > 0
     assert t["default"]["images_per_sec_per_client"] > 0.8 * t["every_32"]["images_per_sec_per_client"]
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs leaves the last timed step's arrays in float32."""
+    import numpy as np
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                        str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = last_json(r.stdout)
+    assert KEYS <= set(j) and j["steps"] == 2 and j["warmup"] == 1 and j["config"]["loss_finite"] == 1
+    assert not {"roofline", "engine_only", "trainer", "secondary", "cpu_baseline"} & set(j)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"loss", "logits", "prob", "trainable", "grad", "momentum"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) < 64 << 20
+    assert got["logits"].shape == got["prob"].shape == (32, 2) and got["trainable"].size == 741952
+    assert abs(float(got["loss"][0]) - j["config"]["final_loss"]) <= 1e-6 * abs(j["config"]["final_loss"])
+    assert np.allclose(got["prob"].sum(1), 1.0, atol=1e-5)
 
 
 def test_two_ranks_launch_path():
@@ -111,7 +130,7 @@ def test_other_baseline_configs_launch_at_two_ranks(cfg, unit, buf):
 
 def test_rn50_config_at_world_one_over_rccl_has_a_roofline():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "FFM_BENCH_ONE_DEVICE")}
-    j = _run_bench(["--config", "c5", "--steps", "5", "--warmup", "2"], env=env, launcher=1)
+    j = _run_bench(["--config", "c5", "--steps", "5", "--warmup", "2", "--full"], env=env, launcher=1)
     assert j["config"]["backend"] == "nccl" and j["config"]["fedavg_buffer_payload_bytes"] > 0
     ro = j["roofline"]
     assert ro["bound"] == "mfma" and 0.01 < ro["frac"] < 1.0 and ro["launches_per_step"] > 100

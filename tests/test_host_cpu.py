@@ -435,6 +435,33 @@ def test_bench_gpus_flag_builds_a_rank_launch(monkeypatch):
     assert "only 1 GPU" in str(e.value.code)
 
 
+def test_bench_plain_run_is_lean_and_full_keeps_the_extras(monkeypatch):
+    """A plain bench line times the K steps only; --full brings back roofline / trainer / secondary / cpu_baseline,
+    each still switched off by its own --no-* flag."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.no_roofline and a.no_trainer and a.no_secondary and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-secondary", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_secondary
+    assert not (a.no_roofline or a.no_trainer or a.no_cpu_baseline)
+
+
+def test_bench_raises_a_smaller_hw_queue_setting(monkeypatch):
+    """The engine's three streams and RCCL's need 8 hardware queues: a 4 already in the environment is raised, a larger
+    value is kept."""
+    import importlib
+    import bench
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", "4")
+    importlib.reload(bench)
+    assert os.environ["GPU_MAX_HW_QUEUES"] == "8"
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", "16")
+    importlib.reload(bench)
+    assert os.environ["GPU_MAX_HW_QUEUES"] == "16"
+
+
 def _ref_style_cfg(mcfg, attribute="race", dataset="FairFedMed"):
     from types import SimpleNamespace as NS
     return NS(INPUT=NS(SIZE=(mcfg.vision.image_size,) * 2, PIXEL_MEAN=list(mcfg.pixel_mean), PIXEL_STD=list(mcfg.pixel_std)),

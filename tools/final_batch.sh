@@ -1,11 +1,13 @@
 set -o pipefail
 V=$1
+: "${BENCH_OUT:?set BENCH_OUT to the directory for <name>_bench.json}"
 cd $GRAFT_REPO_ROOT
 # tools/final_batch.sh <name> [notests]: the round's evidence in one gpurun call (the test suite alone takes ~6 minutes)
 if [ "$2" != "notests" ]; then
 timeout -k 10 900 python -m pytest tests -m gpu -q > gpurun_out/${V}_final_gpu_tests.log 2>&1; echo "tests rc=$?"; tail -2 gpurun_out/${V}_final_gpu_tests.log
 fi
-timeout -k 10 400 python bench.py > gpurun_out/${V}_bench.json 2> gpurun_out/${V}_bench.err; echo "bench rc=$?"; cut -c1-400 gpurun_out/${V}_bench.json
+# the full bench line (roofline, trainer, secondary, cpu_baseline) into $BENCH_OUT
+timeout -k 10 400 python bench.py --full > "$BENCH_OUT/${V}_bench.json" 2> "$BENCH_OUT/${V}_bench.err"; echo "bench rc=$?"; cut -c1-400 "$BENCH_OUT/${V}_bench.json"
 timeout -k 10 300 bash tools/prof.sh ${V} --engine-step && python tools/trace_timeline.py gpurun_out/${V}_kernel_trace.csv 8 > gpurun_out/${V}_timeline.txt
 timeout -k 10 300 bash tools/prof.sh ${V}_serial --serial --engine-step
 timeout -k 10 600 bash tools/pmc.sh ${V} && python tools/pmc_traffic.py gpurun_out/${V}_fetch.csv gpurun_out/${V}_write.csv > gpurun_out/${V}_traffic.json && python tools/sq_counters.py gpurun_out/${V}_sq.csv > gpurun_out/${V}_sq_counters.json
