@@ -4,16 +4,34 @@
 
 namespace {
 
-// torch.optim.SGD, dampening 0, no nesterov (Dassl/dassl/optim/optimizer.py:105-113)
+// torch.optim.SGD, dampening 0, no nesterov (Dassl/dassl/optim/optimizer.py:105-113), `repeats` times on the SAME gradient:
+// d = g + wd*p; b = (first application of a first step) ? d : mu*b + d; p -= lr*b.  Every SGD kernel below goes through
+// this one function, with the roundings written out: left to contraction, the SLP vectoriser pairs mu*b with wd*p into
+// one v_pk_mul_f32 (rounded apart from the adds) in some kernels and some repeats but not in others, and the eager step,
+// its recorded plan and the captured graph must agree bit for bit.  The first application fuses both products into their
+// sums, the later ones round products and sums separately: what ffm_sgd_momentum / _n / _gated have always computed.
+__device__ __forceinline__ void sgd_update(float& pi, float& b, float gi, float lr, float mu, float wd, int first,
+                                           int repeats) {
+    const float d0 = fmaf(wd, pi, gi);
+    b = first ? d0 : fmaf(mu, b, d0);
+    pi = fmaf(-lr, b, pi);
+    for (int k = 1; k < repeats; ++k) {
+#pragma clang fp contract(off)
+        const float d = gi + wd * pi;
+        b = mu * b + d;
+        pi = fmaf(-lr, b, pi);
+    }
+}
+
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                   float* __restrict__ buf, int64_t n, float lr, float mu, float wd,
                                                   int first) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        const float d = g[i] + wd * pi;
-        const float b = first ? d : mu * buf[i] + d;
+        float pi = p[i];
+        float b = first ? 0.f : buf[i];
+        sgd_update(pi, b, g[i], lr, mu, wd, first, 1);
         buf[i] = b;
-        p[i] = pi - lr * b;
+        p[i] = pi;
     }
 }
 
@@ -25,13 +43,8 @@ __global__ __launch_bounds__(256) void sgd_n_kernel(float* __restrict__ p, const
                                                     int first, int repeats) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float pi = p[i];
-        const float gi = g[i];
         float b = first ? 0.f : buf[i];
-        for (int k = 0; k < repeats; ++k) {
-            const float d = gi + wd * pi;
-            b = (first && k == 0) ? d : mu * b + d;
-            pi = pi - lr * b;
-        }
+        sgd_update(pi, b, g[i], lr, mu, wd, first, repeats);
         buf[i] = b;
         p[i] = pi;
     }
@@ -39,16 +52,20 @@ __global__ __launch_bounds__(256) void sgd_n_kernel(float* __restrict__ p, const
 
 // same update with the hyper-parameters read from device memory (hp = {lr, momentum, weight_decay}),
 // so that a captured hipGraph keeps working when the LR scheduler changes lr.  With a zero-initialised
-// momentum buffer the general formula equals torch's first-step rule (mu*0 + d == d exactly).
+// momentum buffer the general formula equals torch's first-step rule (mu*0 + d == d exactly).  st (may be NULL): the
+// fp16 gradient-scale state; the update is skipped when st[2] == 0, as in sgd_gated_kernel.
 __global__ __launch_bounds__(256) void sgd_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ buf, int64_t n,
-                                                      const float* __restrict__ hp) {
+                                                      const float* __restrict__ hp, int repeats,
+                                                      const float* __restrict__ st) {
+    if (st && st[2] == 0.0f) return;              // the gradients overflowed: the step is skipped, momentum untouched
     const float lr = hp[0], mu = hp[1], wd = hp[2];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        const float b = mu * buf[i] + (g[i] + wd * pi);
+        float pi = p[i];
+        float b = buf[i];
+        sgd_update(pi, b, g[i], lr, mu, wd, 0, repeats);
         buf[i] = b;
-        p[i] = pi - lr * b;
+        p[i] = pi;
     }
 }
 
@@ -165,13 +182,8 @@ __global__ __launch_bounds__(256) void sgd_gated_kernel(float* __restrict__ p, c
     if (st[2] == 0.0f) return;                    // the gradients overflowed: the step is skipped, momentum untouched
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float pi = p[i];
-        const float gi = g[i];
         float b = first ? 0.f : buf[i];
-        for (int k = 0; k < repeats; ++k) {
-            const float d = gi + wd * pi;
-            b = (first && k == 0) ? d : mu * b + d;
-            pi = pi - lr * b;
-        }
+        sgd_update(pi, b, g[i], lr, mu, wd, first, repeats);
         buf[i] = b;
         p[i] = pi;
     }
@@ -217,10 +229,16 @@ extern "C" int ffm_sgd_momentum_n(float* p, const float* g, float* buf, int64_t 
     return FFM_OK;
 }
 
-extern "C" int ffm_sgd_momentum_dev(float* p, const float* g, float* buf, int64_t n, const float* hp, void* stream) {
-    if (!p || !g || !buf || !hp || n <= 0) return FFM_EINVAL;
-    hipLaunchKernelGGL(sgd_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, hp);
+extern "C" int ffm_sgd_momentum_dev(float* p, const float* g, float* buf, int64_t n, const float* hp, int repeats,
+                                    float* state, void* stream) {
+    if (!p || !g || !buf || !hp || n <= 0 || repeats < 1 || repeats > 16) return FFM_EINVAL;
+    hipLaunchKernelGGL(sgd_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, hp, repeats,
+                       state);
     FFM_CHECK_LAUNCH();
+    if (state) {
+        hipLaunchKernelGGL(scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
+        FFM_CHECK_LAUNCH();
+    }
     return FFM_OK;
 }
 

@@ -1210,10 +1210,12 @@ class FairLoRAEngine:
         self.step_plans.clear()
 
     # ------------------------------------------------------------- graph --
-    def capture_train_step(self, batch_size: int, lr: float, momentum: float, weight_decay: float) -> "GraphedStep":
+    def capture_train_step(self, batch_size: int, lr: float, momentum: float, weight_decay: float,
+                           repeats: int = 1) -> "GraphedStep":
         """Capture forward + backward + SGD (all three streams) into one hipGraph.  A step then costs the
-        host one graph launch instead of ~450 Python->C calls (the eager loop is host-bound at ~7 ms)."""
-        return GraphedStep(self, batch_size, lr, momentum, weight_decay)
+        host one graph launch instead of ~450 Python->C calls (the eager loop is host-bound at ~7 ms).  A replay trains
+        as forward_backward + sgd_step(lr, momentum, weight_decay, repeats) does, fp16 gradient-scale gating included."""
+        return GraphedStep(self, batch_size, lr, momentum, weight_decay, repeats)
 
     def trainable_state(self) -> Dict[str, Tensor]:
         return {k: self.params.view(k) for k in self.params.keys}
@@ -1223,8 +1225,12 @@ class GraphedStep:
     """One captured training step.  ``run(image, attr, label)`` copies the batch into the static input
     buffers and replays the graph; results are the engine's usual device tensors (loss, logits, prob, finite)."""
 
-    def __init__(self, eng: FairLoRAEngine, batch_size: int, lr: float, momentum: float, weight_decay: float):
+    def __init__(self, eng: FairLoRAEngine, batch_size: int, lr: float, momentum: float, weight_decay: float,
+                 repeats: int = 1):
+        if not 1 <= repeats <= 16:
+            raise ValueError(f"repeats must be 1..16, got {repeats}")
         self.eng = eng
+        self.repeats = repeats
         eng.use_replay = False                        # the hipGraph replaces the recorded launch plan
         v, dev = eng.cfg.vision, eng.device
         self.image = torch.zeros(batch_size, 3, v.image_size, v.image_size, device=dev)
@@ -1234,7 +1240,16 @@ class GraphedStep:
         p = eng.params
         if p.steps == 0:
             p.momentum.zero_()
-        keep = (p.flat.clone(), p.momentum.clone(), p.grad.clone())
+        # everything a body writes that outlives a step: the weights, their momentum and gradients, the loss flag and (fp16)
+        # the gradient-scale state, which the gated update moves
+        live = [p.flat, p.momentum, p.grad, eng.finite] + ([eng.scale_state] if eng.scale_state is not None else [])
+        keep, steps = [t.clone() for t in live], p.steps
+
+        def restore():
+            for t, k in zip(live, keep):
+                t.copy_(k)
+            p.steps = steps
+
         # warm-up off the default stream (sets kernel attributes, sizes the allocator), then restore the state
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -1243,18 +1258,19 @@ class GraphedStep:
                 self._body()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        p.flat.copy_(keep[0]); p.momentum.copy_(keep[1]); p.grad.copy_(keep[2])
+        restore()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = self._body()
-        p.flat.copy_(keep[0]); p.momentum.copy_(keep[1]); p.grad.copy_(keep[2])
+        restore()
         torch.cuda.synchronize(dev)
 
     def _body(self):
         out = self.eng.forward_backward(self.image, self.attr, self.label)
         with torch.no_grad():
             p = self.eng.params
-            ops.sgd_momentum_dev(p.flat, p.grad, p.momentum, self.hp)
+            # fp16: skipped when the gradients overflowed, then the scale moves (as sgd_step's gated update)
+            ops.sgd_momentum_dev(p.flat, p.grad, p.momentum, self.hp, self.repeats, self.eng.scale_state)
         return out
 
     def set_lr(self, lr: float) -> None:
@@ -1268,5 +1284,5 @@ class GraphedStep:
         if label is not None:
             self.label.copy_(label, non_blocking=True)
         self.graph.replay()
-        self.eng.params.steps += 1
+        self.eng.params.steps += self.repeats
         return self.out

@@ -836,10 +836,14 @@ def sgd_momentum_gated(p: Tensor, g: Tensor, buf: Tensor, lr: float, momentum: f
           weight_decay, int(first_step), int(repeats), L.ptr(_f32(state)), L.stream_ptr())
 
 
-def sgd_momentum_dev(p: Tensor, g: Tensor, buf: Tensor, hp: Tensor) -> None:
-    _dev(p, g, buf, hp)
+def sgd_momentum_dev(p: Tensor, g: Tensor, buf: Tensor, hp: Tensor, repeats: int = 1,
+                     state: Optional[Tensor] = None) -> None:
+    """sgd_momentum with hp = {lr, momentum, weight_decay} in device memory and a zeroed buf for the first step; with the
+    fp16 gradient-scale state it is gated and moves the scale as sgd_momentum_gated does (ffm_sgd_momentum_dev)."""
+    _dev(p, g, buf, hp, state)
+    assert state is None or state.numel() == SCALE_STATE
     _call("ffm_sgd_momentum_dev", L.ptr(_f32(p)), L.ptr(_f32(g)), L.ptr(_f32(buf)), p.numel(), L.ptr(_f32(hp)),
-                                          L.stream_ptr())
+          int(repeats), L.ptr(_f32(state)), L.stream_ptr())
 
 
 def scale_by(p: Tensor, w: Tensor, out: Tensor) -> None:

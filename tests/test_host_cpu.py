@@ -112,6 +112,36 @@ def test_integration_md_stub_mirrors_gemm_args():
     assert [(n, kinds[k]) for n, k in names] == [(n, t) for n, t in _lib.GemmArgs._fields_]
 
 
+def test_ctypes_signatures_match_the_header_prototypes():
+    """Every _lib.SIGNATURES entry against its prototype in include/ffm_hip.h: the same number of arguments, scalars of
+    exactly the C type (float -> c_float, int / int32_t -> c_int32, int64_t -> c_int64), a ctypes pointer type for every
+    pointer (a typed one on the pointee's type), and the return type load() sets.  An argument list one off passes a float
+    or an int where the library expects a pointer, and nothing else notices until the kernel faults."""
+    from fairfedmed_amd import build as B
+    protos = {n: (rt, [t for t, _ in params]) for rt, n, params in B.api_prototypes()}
+    # build.api_prototypes() takes the int / void returns the dispatcher needs; the two int64_t size queries besides them
+    hdr = re.sub(r"/\*.*?\*/", "", open(B.HEADER).read(), flags=re.S)
+    for name, args in re.findall(r"\n\s*int64_t\s+(ffm_\w+)\s*\(([^;{}]*?)\)\s*;", hdr):
+        protos[name] = ("int64_t", [re.match(r"^(.*?)\w+$", a.strip()).group(1).strip() for a in " ".join(args.split()).split(",")])
+    assert set(protos) == set(_lib.SIGNATURES), set(protos) ^ set(_lib.SIGNATURES)
+    scalar = {"float": ctypes.c_float, "int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+    pointee = {"float": ctypes.c_float, "int32_t": ctypes.c_int32, "int": ctypes.c_int32, "int64_t": ctypes.c_int64,
+               "ffm_gemm_args": _lib.GemmArgs, "ffm_pack_desc": _lib.PackDesc, "ffm_reduce_desc": _lib.ReduceDesc}
+    lib = _lib.load()
+    for name, argtypes in _lib.SIGNATURES.items():
+        rt, ctypes_wanted = protos[name]
+        assert len(argtypes) == len(ctypes_wanted), (name, len(argtypes), ctypes_wanted)
+        for i, (c, got) in enumerate(zip(ctypes_wanted, argtypes)):
+            if "*" in c:
+                assert isinstance(got, type) and issubclass(got, (ctypes.c_void_p, ctypes._Pointer)), (name, i, c, got)
+                base = c.replace("const", "").replace("*", "").strip()
+                if issubclass(got, ctypes._Pointer):
+                    assert got._type_ is pointee.get(base), (name, i, c, got)
+            else:
+                assert c in scalar and got is scalar[c], (name, i, c, got)
+        assert getattr(lib, name).restype is {"int": ctypes.c_int, "int64_t": ctypes.c_int64}[rt], (name, rt)
+
+
 def test_registry_semantics():
     r = Registry("T")
 
