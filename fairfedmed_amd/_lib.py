@@ -20,7 +20,8 @@ F32_X3_W16 = 4                           # FFM_F32_X3 with the weight operand st
 EPI_BIAS, EPI_LORA, EPI_LORA_KR, EPI_RESIDUAL, EPI_GELU, EPI_DGELU, EPI_RANKOP = 1, 2, 4, 8, 16, 32, 64
 EPI_ROWSTATS, EPI_LNIN, EPI_LGRAD, EPI_BNBWD = 128, 256, 512, 1024
 EPI_LNB_STAT, EPI_LNB_APPLY = 2048, 4096
-ABI_VERSION = 13
+EPI_GELU_ONLY = 8192       # with EPI_GELU: `c` receives the activation, nothing else is stored (the evaluation pass)
+ABI_VERSION = 14
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 

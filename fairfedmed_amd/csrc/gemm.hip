@@ -814,14 +814,16 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(gemm_kargs px) {
                     }
                 }
                 float gd[8];
-                const bool deriv = (flags & FFM_EPI_GELU) && p.gelu_deriv;
+                // GELU_ONLY (evaluation pass): the activation goes to `c` and the pre-activation is not stored at all
+                const bool act_only = (flags & FFM_EPI_GELU_ONLY) != 0;
+                const bool deriv = (flags & FFM_EPI_GELU) && !act_only && p.gelu_deriv;
                 if (deriv) {
                     float ga[8];
 #pragma unroll
                     for (int c = 0; c < 8; ++c) Act<T>::gelu_both(Elem<T>::to_f(Elem<T>::from_f(v[i][c])), ga[c], gd[c]);
                     Vec8<T>::store(C + off, gd);
                     Vec8<T>::store(reinterpret_cast<T*>(p.c2) + off, ga);
-                } else {
+                } else if (!act_only) {
                     Vec8<T>::store(C + off, v[i]);
                 }
                 if (BNB && cst && bnb) {
@@ -848,7 +850,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(gemm_kargs px) {
                     float a[8];
 #pragma unroll
                     for (int c = 0; c < 8; ++c) a[c] = Act<T>::gelu(Elem<T>::to_f(Elem<T>::from_f(v[i][c])));
-                    Vec8<T>::store(reinterpret_cast<T*>(p.c2) + off, a);
+                    Vec8<T>::store((act_only ? C : reinterpret_cast<T*>(p.c2)) + off, a);
                 }
             }
         }
@@ -957,6 +959,8 @@ __global__ __launch_bounds__(256) void lora_pack_ln_kernel(const ffm_pack_desc* 
 extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
     if (!args || !args->a || !args->b || !args->c) return FFM_EINVAL;
     const ffm_gemm_args& a = *args;
+    // FFM_EPI_GELU_ONLY is a variant of the GELU epilogue and has no derivative form
+    if ((a.flags & FFM_EPI_GELU_ONLY) && (!(a.flags & FFM_EPI_GELU) || a.gelu_deriv)) return FFM_EINVAL;
     const size_t es = dtype == FFM_BF16 ? 2 : 4;
     const size_t esb = dtype == FFM_F32_X3_W16 ? 2 : es;                  // (FFM_F32_X3_W16: f32 activations, half weights)
     if (dtype != FFM_BF16 && dtype != FFM_F32 && dtype != FFM_F32_X3 && dtype != FFM_F32_X3_W16) return FFM_EINVAL;
@@ -974,7 +978,8 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
     }
     if ((a.flags & FFM_EPI_BIAS) && !a.bias) return FFM_EINVAL;
     if ((a.flags & FFM_EPI_RESIDUAL) && (!a.res || ((uintptr_t)a.res & 15))) return FFM_EINVAL;
-    if ((a.flags & FFM_EPI_GELU) && (!a.c2 || ((uintptr_t)a.c2 & 15))) return FFM_EINVAL;
+    // (FFM_EPI_GELU_ONLY: c2 is neither read nor written)
+    if ((a.flags & FFM_EPI_GELU) && !(a.flags & FFM_EPI_GELU_ONLY) && (!a.c2 || ((uintptr_t)a.c2 & 15))) return FFM_EINVAL;
     if ((a.flags & FFM_EPI_DGELU) && (!a.aux || ((uintptr_t)a.aux & 15))) return FFM_EINVAL;
     if (a.flags & FFM_EPI_BNBWD) {                                        // BatchNorm-backward column sums: 128x128 kernel
         if (!a.colstat_part || !a.bn_x || !a.bn_mean || !a.bn_rstd || (a.flags & FFM_EPI_GELU)) return FFM_EINVAL;
@@ -1033,6 +1038,7 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
     if (rk) {
         switch (fl) {
             FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)                        // c_fc forward
+            FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)    // ... of the evaluation pass
             FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)                    // c_proj forward
             FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU)                    // dX of c_proj
             FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR)                                    // dX of c_fc
@@ -1049,9 +1055,11 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
         FFM_GEMM_CASE(false, FFM_EPI_BIAS)
         FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_RESIDUAL)
         FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_GELU)
+        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)
         FFM_GEMM_CASE(false, FFM_EPI_DGELU)
         FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA)
         FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)
+        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)
         FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)
         FFM_GEMM_CASE(false, FFM_EPI_LORA | FFM_EPI_LORA_KR)
         FFM_GEMM_CASE(false, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU)

@@ -73,6 +73,9 @@ bool rk_flags_ok(int flags, int rank) {
 // Cost model (both kernels are bound by the bytes a CU pulls through its texture path): rounds x operand rows
 // loaded per K step.  The 128x128 kernel runs two blocks per CU, so a CU with two tiles loads 2 x 256 rows.
 int ffm_panel_select(int M, int N, int K, int flags, int rank, int dtype, bool packed) {
+    // FFM_EPI_GELU_ONLY changes what the GELU epilogue stores, never the tile: every query built on this function (tile
+    // shape, tiles_m / tiles_n, the LayerNorm folds) answers as without it, so the evaluation pass folds what training folds
+    flags &= ~FFM_EPI_GELU_ONLY;
     if (!packed || dtype != FFM_BF16 || K % 128 != 0 || K < 512) return -1;
     const bool rk = (flags & FFM_EPI_RANKOP) != 0;
     if (rk ? !rk_flags_ok(flags, rank) : !plain_flags_ok(flags)) return -1;

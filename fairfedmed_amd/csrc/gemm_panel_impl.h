@@ -153,6 +153,8 @@ __attribute__((amdgpu_waves_per_eu(panel_waves_per_eu<MF, NF, RK, PWV>(), panel_
     static_assert(!LNBA || (!KS && !(FL & (FFM_EPI_RESIDUAL | FFM_EPI_DGELU | FFM_EPI_GELU | FFM_EPI_LNIN | FFM_EPI_ROWSTATS | FFM_EPI_BIAS))),
                   "LNB_APPLY: a dX epilogue without anything else in it (FairLoRA: c_fc; plain: the in-projection)");
     static_assert(RK || !(flags & FFM_EPI_LORA), "the panel kernel only has the in-kernel (RANKOP) LoRA epilogue");
+    static_assert(!(FL & FFM_EPI_GELU_ONLY) || ((FL & FFM_EPI_GELU) && !(FL & (FFM_EPI_RESIDUAL | FFM_EPI_DGELU))),
+                  "GELU_ONLY is a variant of the GELU epilogue (no prefetched rows, so no counted waits beside its stores)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -772,7 +774,8 @@ __attribute__((amdgpu_waves_per_eu(panel_waves_per_eu<MF, NF, RK, PWV>(), panel_
     // the rest of its batch, groups q-PF+1 .. q-1 (NF * SPC stores each, plus a batch of NF loads while one is left to
     // issue), and this group's stores so far.  Exact when every lane stores (full tiles); the last group of an odd MF
     // has chunks without rows, so its own stores are not counted (waits a little longer than needed).
-    constexpr int SPC = (flags & FFM_EPI_GELU) ? 2 : 1;
+    // (FFM_EPI_GELU_ONLY stores the activation alone: one store per chunk)
+    constexpr int SPC = ((flags & FFM_EPI_GELU) && !(flags & FFM_EPI_GELU_ONLY)) ? 2 : 1;
     const bool full_tile = m0 + BMp <= p.M;
     if constexpr (PRE) {
 #pragma unroll
@@ -1126,6 +1129,23 @@ __attribute__((amdgpu_waves_per_eu(panel_waves_per_eu<MF, NF, RK, PWV>(), panel_
             if (ok) {
                 const size_t off = (size_t)gm * p.ldc + n0w + ch * 8;
                 if constexpr ((flags & FFM_EPI_GELU) != 0) {
+#ifdef FFM_TWIN_F16
+                    // Half storage: pin x to the fp32 value that is then rounded to storage.  Left alone, the compiler folds
+                    // fptrunc(fma) - LNIN's rs * (..) + d - into one single-rounding v_fma_mixlo_f16 for whichever elements
+                    // its vectoriser leaves scalar (one of eight in the two-output epilogue, none in the activation-only
+                    // one): FFM_EPI_GELU_ONLY's `c` was one 16-bit ulp off the two-output `c2` in 6 of a million elements.
+                    // (bf16 has no mixed-precision FMA: its code is as it was.)
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) asm volatile("" : "+v"(v[c]));
+#endif
+                }
+                if constexpr ((flags & FFM_EPI_GELU_ONLY) != 0) {
+                    // the evaluation pass: c = gelu(x), x rounded as the two-output epilogue stores it; nothing else leaves
+                    float a[8];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) a[c] = Act<bf16_t>::gelu((float)(bf16_t)v[c]);
+                    Vec8<bf16_t>::store(C + off, a);
+                } else if constexpr ((flags & FFM_EPI_GELU) != 0) {
                     float a[8];
                     if (p.gelu_deriv) {                          // c = gelu'(x), c2 = gelu(x), x as it would have been stored
                         float d[8];

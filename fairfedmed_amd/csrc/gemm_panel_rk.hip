@@ -19,6 +19,8 @@ static int ffm_panel_launch_rk1(const ffm_gemm_args& a, int cfg, hipStream_t s) 
     switch (a.flags & ~FFM_EPI_RANKOP) {
         PANEL_RK_CASE(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)                          // c_fc forward
         PANEL_RK_CASE(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_LNIN)           // ... with ln_2 folded in
+        PANEL_RK_CASE(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)                  // c_fc of the evaluation pass: the activation alone
+        PANEL_RK_CASE(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY | FFM_EPI_LNIN)   // ... with ln_2 folded in
         PANEL_RK_CASE(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)                      // c_proj forward
         case FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL | FFM_EPI_ROWSTATS:            // ... leaving row sums for ln_1
             // (the 128-column tiles only: a row's lanes must form a power-of-two group)

@@ -187,6 +187,32 @@ class _Block:
         return self.packed[name] if self.packed else None
 
 
+@dataclass
+class _LayerBufs:
+    """What one residual block of `_stack_forward` reads and writes, cut to the rows in use.  Two providers: `_Stack.layer`
+    (training: one set per layer, everything the backward needs) and `_InferWorkspace.layer` (evaluation: one set for all
+    layers, the optional outputs None).  pre None: the c_fc product stores the activation alone (FFM_EPI_GELU_ONLY)."""
+    x: Tensor                                  # block input
+    xm: Tensor                                 # after the attention residual
+    qkv: Tensor
+    o: Tensor
+    h: Tensor                                  # ln_1 output (unfolded route)
+    h2: Tensor                                 # ln_2 output (unfolded route)
+    pre: Optional[Tensor]
+    act: Tensor
+    x_out: Tensor                              # block output = the next block's input
+    lse: Optional[Tensor] = None
+    st1: Tuple[Optional[Tensor], Optional[Tensor]] = (None, None)      # ln_1 mean / rstd
+    st2: Tuple[Optional[Tensor], Optional[Tensor]] = (None, None)
+    rowp: Optional[Tensor] = None              # partial row sums of x (ln_1 folded into qkv), of x_out, of xm (ln_2 into c_fc)
+    rowp_out: Optional[Tensor] = None
+    rowp2: Optional[Tensor] = None
+    t1: Optional[Tensor] = None                # rank vectors of c_fc / c_proj: outputs of the fused route (optional there),
+    ts1: Optional[Tensor] = None               # operands of the rank > 16 route
+    t2: Optional[Tensor] = None
+    ts2: Optional[Tensor] = None
+
+
 class _Stack:
     """A transformer tower (vision with FairLoRA, or text) with its saved activations."""
 
@@ -285,6 +311,80 @@ class _Stack:
             self.plans = {}
             self.lgrad = {}                                      # rows -> row tiles of the FFM_EPI_LGRAD partials (0: not served)
 
+    def layer(self, i: int, rows: int) -> _LayerBufs:
+        """Block i's share of the stash (everything the backward pass reads), cut to `rows`."""
+        r = self.rank
+        return _LayerBufs(self.x[i][:rows], self.xm[i][:rows], self.qkv[i][:rows], self.o[i][:rows], self.h[:rows],
+                          self.h2[i][:rows], self.pre[i][:rows], self.act[i][:rows], self.x[i + 1][:rows], self.lse[i],
+                          self.st1[i], self.st2[i], self.rowp[i] if self.rowp is not None else None,
+                          self.rowp[i + 1] if self.rowp is not None else None,
+                          self.rowp2[i] if self.rowp2 is not None else None,
+                          self.t1[i] if r else None, self.ts1[i] if r else None, self.t2[i] if r else None,
+                          self.ts2[i] if r else None)
+
+
+class _InferWorkspace:
+    """Buffers of the forward-only evaluation pass (FairLoRAEngine.infer) for up to `max_images` ViT images.  Nothing is
+    kept for a backward pass, so one set of layer buffers serves every block - the residual stream ping-pongs between two
+    buffers - and the size does not depend on the depth of the tower: (2 + 1 + 3 + 1 + 2 + 4) x width 16-bit values per token
+    row (x twice, xm, qkv, o, h / h2, the activation) against ~20 x width per row AND LAYER in the training stash.  It shares
+    nothing writable with that stash: patch columns, embeddings, features, head and transport buffers are its own too.
+    Attribute names follow the engine's, so `_vision_forward` / `_head_forward` take either as their buffer set."""
+
+    def __init__(self, eng: "FairLoRAEngine", max_images: int):
+        cfg, v, dtype, dev = eng.cfg, eng.cfg.vision, eng.dtype, eng.device
+        self.max_images = max_images
+        T, w, P, r = max_images * v.tokens, v.width, v.grid * v.grid, cfg.lora.rank
+        f32 = torch.float32
+        e = lambda *s: torch.zeros(*s, device=dev, dtype=dtype)
+        f = lambda *s: torch.zeros(*s, device=dev, dtype=f32)
+        self.xs = (e(T, w), e(T, w))
+        self.xm, self.qkv, self.o, self.h, self.h2, self.act = e(T, w), e(T, 3 * w), e(T, w), e(T, w), e(T, w), e(T, 4 * w)
+        fold = bool(r) and _is16(dtype)                   # as _Stack: the partial row sums of the LayerNorm folds
+        self.rowps = (f(8 * T * 2), f(8 * T * 2)) if fold else None
+        self.rowp2 = f(8 * T * 2) if fold else None
+        # rank > 16: the down projections are launches of their own and t / ts their operands (one pair: c_fc's is dead
+        # when c_proj's is formed)
+        self.t, self.ts = (f(T, r), f(T, r)) if (r and not eng.fused_rank) else (None, None)
+        self.cols = e(max_images * P, 3 * v.patch * v.patch)
+        self.patch_out = e(max_images * P, w)
+        self.hpost = e(T, w)
+        self.post_stats = (None, None)
+        self.feat = e(T, v.out_dim)
+        self.fbar = f(max_images, v.out_dim)
+        self.rnorm = f(T)
+        self.logits_img = f(max_images, cfg.n_cls)
+        self.attr_i32 = torch.zeros(max_images, device=dev, dtype=torch.int32)
+        if eng.is3d:
+            H = v.image_size
+            self.conv_out = f(max_images, 3, H, H)
+            self.mm_part = f(max_images * ops.slice_blocks(H, H) * 2)
+            self.mnmx = f(max_images, 2)
+            self.mm_cnt = torch.zeros(max_images, 2, device=dev, dtype=torch.int32)
+        if eng.ot:
+            n = max_images * cfg.n_cls * (v.tokens - 1) * cfg.n_prompts
+            self.ot_sim, self.ot_T = f(n), f(n)
+            self.ot_errs = f(cfg.ot_max_iter * max_images * cfg.n_cls)
+            self.ot_istop = torch.zeros(1, device=dev, dtype=torch.int32)
+            self.ot_tsum = f(max_images * cfg.n_cls)
+
+    def layer(self, i: int, rows: int) -> _LayerBufs:
+        a, b = self.xs[i & 1], self.xs[(i + 1) & 1]
+        rp = self.rowps
+        return _LayerBufs(a[:rows], self.xm[:rows], self.qkv[:rows], self.o[:rows], self.h[:rows], self.h2[:rows], None,
+                          self.act[:rows], b[:rows], rowp=rp[i & 1] if rp else None, rowp_out=rp[(i + 1) & 1] if rp else None,
+                          rowp2=self.rowp2, t1=self.t, ts1=self.ts, t2=self.t, ts2=self.ts)
+
+    def nbytes(self) -> int:
+        """Bytes of device memory the workspace holds."""
+        seen, n = set(), 0
+        for val in vars(self).values():
+            for t in (val if isinstance(val, tuple) else (val,)):
+                if isinstance(t, Tensor) and t.data_ptr() not in seen:
+                    seen.add(t.data_ptr())
+                    n += t.numel() * t.element_size()
+        return n
+
 
 class FairLoRAEngine:
     """HIP execution engine for CustomCLIP(+FairLoRA) training and inference."""
@@ -314,7 +414,9 @@ class FairLoRAEngine:
         return int(self.scale_state[4]) if self.scale_state is not None else 0
 
     def __init__(self, cfg: ModelCfg, state_dict: Dict[str, Tensor], dtype=torch.bfloat16, max_images: int = 32,
-                 device: str = "cuda:0"):
+                 device: str = "cuda:0", max_infer_images: Optional[int] = None):
+        """max_images sizes the training stash (forward / forward_backward), max_infer_images (default: max_images) the
+        depth-independent workspace of the forward-only pass (infer)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FairLoRAEngine needs an MI355X GPU; there is no CPU path")
         from . import _lib
@@ -423,6 +525,9 @@ class FairLoRAEngine:
         self.ev_start = torch.cuda.Event()
         self.ev_pack = torch.cuda.Event()
         self._pack_event = None
+        self.max_infer_images = max_images if max_infer_images is None else int(max_infer_images)
+        self._in_session = False
+        self._init_infer()
 
     # ---------------------------------------------------- vision tower hooks --
     def _init_vision(self, max_images: int) -> None:
@@ -488,6 +593,12 @@ class FairLoRAEngine:
                     ent.append((self.params.view(blk.lora["fc_A"]), False, pk["fc_A_ln"], None,
                                 (blk.ln2_w, blk.ln2_b, pk["fc_A_lnrk"])))
             self.pack_plan = ops.PackPlan(ent, dtype, dev)
+
+    def _init_infer(self) -> None:
+        """The evaluation pass's workspace (RN50: none, engine_rn.py)."""
+        if self.max_infer_images < 1:
+            raise ValueError(f"max_infer_images must be positive, got {self.max_infer_images}")
+        self.infer_ws = _InferWorkspace(self, self.max_infer_images)
 
     def _n_layer_events(self) -> int:
         return self.cfg.vision.layers
@@ -666,62 +777,70 @@ class FairLoRAEngine:
         return st.foldb1[rows]
 
     def _stack_forward(self, st: _Stack, rows: int, images: int, attr: Optional[Tensor], rows_per_sample: int,
-                       save: bool = True) -> Tensor:
-        """x[0][:rows] holds the tower input; returns the tower output view."""
+                       bufs=None) -> Tensor:
+        """The tower input is in layer 0's `x`; returns the tower output view.  bufs: the provider of every block's
+        `_LayerBufs` - the tower's own stash (default: training and forward()) or an `_InferWorkspace`, whose sets have no
+        pre-activation, no rank vectors and no statistics: the same launches in the same order, fewer stores."""
         lo = self.cfg.lora
         r, G = st.rank, lo.num_groups
         gemm = st.gemm
+        bufs = st if bufs is None else bufs
+        out = lb = None
+
+        def fc(a, w, **k):
+            # c_fc + QuickGELU of the current block: pre-activation and activation (the backward reads both), or the
+            # activation alone
+            if lb.pre is None:
+                gemm(a, w, lb.act, gelu_only=True, **k)
+            else:
+                gemm(a, w, lb.pre, gelu_out=lb.act, **k)
         for i, blk in enumerate(st.blocks):
-            x, xm = st.x[i][:rows], st.xm[i][:rows]
-            qkv, o, h2 = st.qkv[i][:rows], st.o[i][:rows], st.h2[i][:rows]
-            pre, act = st.pre[i][:rows], st.act[i][:rows]
-            h = st.h[:rows]
+            lb = bufs.layer(i, rows)
+            x, xm, qkv, o, h, h2, act = lb.x, lb.xm, lb.qkv, lb.o, lb.h, lb.h2, lb.act
             fold = self._fold_ln1(st, rows)
             if fold:
                 # ln_1 rides inside the qkv product: raw rows x gamma-scaled weight, normalised in the epilogue with the
                 # row sums the producer of x left behind (block 0: embed_lnpre, else the previous block's c_proj)
-                ln = ops.LnIn(st.rowp[i], 1 if i == 0 else fold, blk.c_in, st.st1[i][0], st.st1[i][1])
+                ln = ops.LnIn(lb.rowp, 1 if i == 0 else fold, blk.c_in, lb.st1[0], lb.st1[1])
                 gemm(x, blk.w_in_ln, qkv, bias=blk.d_in, b_packed=blk.pk("w_in_ln"), ln_in=ln)
             else:
-                ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, st.st1[i][0], st.st1[i][1])
+                ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
                 gemm(h, blk.w_in, qkv, bias=blk.b_in, b_packed=blk.pk("w_in"))
-            ops.attention_fwd(qkv, o, st.lse[i], images, st.L, st.heads, st.causal)
+            ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
             fold2 = self._fold_ln2(st, rows) if r else 0
-            gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=st.rowp2[i] if fold2 else None)
+            gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=lb.rowp2 if fold2 else None)
             if not fold2:
-                ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, st.st2[i][0], st.st2[i][1])
+                ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, lb.st2[0], lb.st2[1])
             if r and self.fused_rank:
                 if fold2:
                     # ln_2 rides inside the c_fc product (h2 is never written; dA(c_fc) takes the raw rows, _stack_backward)
                     ro = ops.RankOp(self.rk[i]["fc_A_ln"], self._S(i, "fc"), attr, rows_per_sample, lo.scaling,
-                                    lo.lambda_group, t_out=st.t1[i], ts_out=st.ts1[i], lw_wide=self.lw_wide[i].get("fc_B"))
-                    ln = ops.LnIn(st.rowp2[i], fold2, blk.c_fc, st.st2[i][0], st.st2[i][1], rk=self.rk[i]["fc_A_lnrk"])
-                    gemm(xm, blk.w_fc_ln, pre, bias=blk.d_fc, lw=self._lora_view(blk, "fc_B"), gelu_out=act, rankop=ro,
-                         b_packed=blk.pk("w_fc_ln"), ln_in=ln)
+                                    lo.lambda_group, t_out=lb.t1, ts_out=lb.ts1, lw_wide=self.lw_wide[i].get("fc_B"))
+                    ln = ops.LnIn(lb.rowp2, fold2, blk.c_fc, lb.st2[0], lb.st2[1], rk=self.rk[i]["fc_A_lnrk"])
+                    fc(xm, blk.w_fc_ln, bias=blk.d_fc, lw=self._lora_view(blk, "fc_B"), rankop=ro,
+                       b_packed=blk.pk("w_fc_ln"), ln_in=ln)
                 else:
                     ro = ops.RankOp(self.rk[i]["fc_A"], self._S(i, "fc"), attr, rows_per_sample, lo.scaling,
-                                    lo.lambda_group, t_out=st.t1[i], ts_out=st.ts1[i], lw_wide=self.lw_wide[i].get("fc_B"))
-                    gemm(h2, blk.w_fc, pre, bias=blk.b_fc, lw=self._lora_view(blk, "fc_B"), gelu_out=act, rankop=ro,
-                         b_packed=blk.pk("w_fc"))
+                                    lo.lambda_group, t_out=lb.t1, ts_out=lb.ts1, lw_wide=self.lw_wide[i].get("fc_B"))
+                    fc(h2, blk.w_fc, bias=blk.b_fc, lw=self._lora_view(blk, "fc_B"), rankop=ro, b_packed=blk.pk("w_fc"))
                 ro = ops.RankOp(self.rk[i]["proj_A"], self._S(i, "proj"), attr, rows_per_sample,
-                                lo.scaling, lo.lambda_group, t_out=st.t2[i], ts_out=st.ts2[i],
+                                lo.scaling, lo.lambda_group, t_out=lb.t2, ts_out=lb.ts2,
                                 lw_wide=self.lw_wide[i].get("proj_B"))
-                gemm(act, blk.w_proj, st.x[i + 1][:rows], bias=blk.b_proj, lw=self._lora_view(blk, "proj_B"),
+                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, lw=self._lora_view(blk, "proj_B"),
                      res=xm, rankop=ro, b_packed=blk.pk("w_proj"),
-                     rowstats=st.rowp[i + 1] if (fold and i + 1 < st.layers) else None)
+                     rowstats=lb.rowp_out if (fold and i + 1 < st.layers) else None)
             elif r:
                 ops.lora_down(h2, self._lora_view(blk, "fc_A"), False, self._S(i, "fc"), attr, r, G,
-                              rows_per_sample, lo.scaling, lo.lambda_group, st.t1[i], st.ts1[i])
-                gemm(h2, blk.w_fc, pre, bias=blk.b_fc, ts=st.ts1[i], lw=self._lora_view(blk, "fc_B"),
-                            gelu_out=act)
+                              rows_per_sample, lo.scaling, lo.lambda_group, lb.t1, lb.ts1)
+                fc(h2, blk.w_fc, bias=blk.b_fc, ts=lb.ts1, lw=self._lora_view(blk, "fc_B"))
                 ops.lora_down(act, self._lora_view(blk, "proj_A"), False, self._S(i, "proj"), attr, r, G,
-                              rows_per_sample, lo.scaling, lo.lambda_group, st.t2[i], st.ts2[i])
-                gemm(act, blk.w_proj, st.x[i + 1][:rows], bias=blk.b_proj, ts=st.ts2[i],
-                            lw=self._lora_view(blk, "proj_B"), res=xm)
+                              rows_per_sample, lo.scaling, lo.lambda_group, lb.t2, lb.ts2)
+                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, ts=lb.ts2, lw=self._lora_view(blk, "proj_B"), res=xm)
             else:
-                gemm(h2, blk.w_fc, pre, bias=blk.b_fc, gelu_out=act)
-                gemm(act, blk.w_proj, st.x[i + 1][:rows], bias=blk.b_proj, res=xm)
-        return st.x[st.layers][:rows]
+                fc(h2, blk.w_fc, bias=blk.b_fc)
+                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, res=xm)
+            out = lb.x_out
+        return out
 
     def _stack_backward(self, st: _Stack, rows: int, images: int, attr: Optional[Tensor], rows_per_sample: int,
                         need_input_grad: bool, grad_in_last: bool = False) -> Tensor:
@@ -970,7 +1089,7 @@ class FairLoRAEngine:
         ops.text_ctx_grad(self.txt.g, self.params.view("prompt_learner.ctx", "grad"), cfg.n_cls, self.txt_len)
 
     # ------------------------------------------------------------- vision --
-    def _as_f32(self, image: Tensor) -> Tensor:
+    def _as_f32(self, image: Tensor, slot: str = "_u8_stage") -> Tensor:
         """uint8 transport (fairfedmed_amd.data, transport="uint8"): expand on the GPU to the float32 batch the
         reference's loader ships - a single SLO / X-ray channel is repeated to 3 (utils/data_utils.py:676-679)."""
         if image.dtype != torch.uint8:
@@ -979,14 +1098,16 @@ class FairLoRAEngine:
             raise TypeError("uint8 images must be CUDA tensors [B, C, H, W]")
         b, c1 = image.shape[:2]
         rep = 1 if self.cfg.dim_per_3d_slice else (3 // c1 if c1 in (1, 3) else 1)
-        stage = getattr(self, "_u8_stage", None)
+        stage = getattr(self, slot, None)             # (the evaluation pass stages in a buffer of its own)
         shape = (b, c1 * rep) + tuple(image.shape[2:])
         if stage is None or stage.shape[0] < b or tuple(stage.shape[1:]) != shape[1:]:
-            stage = self._u8_stage = torch.empty(shape, device=self.device, dtype=torch.float32)
+            stage = torch.empty(shape, device=self.device, dtype=torch.float32)
+            setattr(self, slot, stage)
         return ops.expand_u8(image.contiguous(), stage[:b], rep)
 
-    def _check_batch(self, image: Tensor) -> Tuple[int, int]:
+    def _check_batch(self, image: Tensor, limit: Optional[int] = None, what: str = "max_images") -> Tuple[int, int]:
         cfg, v = self.cfg, self.cfg.vision
+        limit = self.max_images if limit is None else limit
         if not image.is_cuda or image.dtype != torch.float32:
             raise TypeError("image must be a float32 CUDA tensor of raw 0..255 values")
         b, c, h, w = image.shape
@@ -995,52 +1116,67 @@ class FairLoRAEngine:
             raise ValueError(f"expected [B,{'S*%d' % D if D else 3},{v.image_size},{v.image_size}], "
                              f"got {tuple(image.shape)}")
         S = c // D if D else 1                       # slices per sample: the ViT batch is b*S (:683-684)
-        if b * S > self.max_images:
-            raise ValueError(f"{b * S} ViT images exceed the engine's max_images={self.max_images}")
+        if b * S > limit:
+            raise ValueError(f"{b * S} ViT images exceed the engine's {what}={limit}")
         return b, S
 
-    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor]):
-        """Per-step inputs -> static buffers (these three launches are the only ones not replayed)."""
+    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor], ws=None):
+        """Per-step inputs -> static buffers (these three launches are the only ones not replayed).  ws: the evaluation
+        pass's workspace instead of the engine's own (training) buffers."""
         cfg, v = self.cfg, self.cfg.vision
-        image = self._as_f32(image)
-        b, S = self._check_batch(image)
+        if ws is None:
+            image = self._as_f32(image)
+            b, S = self._check_batch(image)
+            ws = self
+        else:
+            image = self._as_f32(image, "_u8_stage_infer")
+            b, S = self._check_batch(image, ws.max_images, "max_infer_images")
         images = b * S
         P = v.grid * v.grid
         if self.is3d:
             # trainable 5x5 slice conv + per-image min-max (trainers/GLP_OT_SVLoRA.py:681-690), then the patches
-            self._image = image.contiguous()
-            ops.slice_conv_fwd(self._image, self.params.view("proj_per_3d_slice.weight"),
-                               self.params.view("proj_per_3d_slice.bias"), self.conv_out[:images], self.mm_part,
-                               self.mnmx, self.mm_cnt, cfg.dim_per_3d_slice)
-            ops.patchify_minmax(self.conv_out[:images], self.mnmx, self.mm_cnt, self.cols[:images * P], v.patch,
+            image = image.contiguous()
+            if ws is self:
+                self._image = image                   # (the backward of the slice convolution reads it)
+            ops.slice_conv_fwd(image, self.params.view("proj_per_3d_slice.weight"),
+                               self.params.view("proj_per_3d_slice.bias"), ws.conv_out[:images], ws.mm_part,
+                               ws.mnmx, ws.mm_cnt, cfg.dim_per_3d_slice)
+            ops.patchify_minmax(ws.conv_out[:images], ws.mnmx, ws.mm_cnt, ws.cols[:images * P], v.patch,
                                 cfg.pixel_mean, cfg.pixel_std)
         else:
-            ops.patchify(image.contiguous(), self.cols[:images * P], v.patch, cfg.pixel_mean, cfg.pixel_std)
+            ops.patchify(image.contiguous(), ws.cols[:images * P], v.patch, cfg.pixel_mean, cfg.pixel_std)
         if attr is not None:
-            self.attr_i32[:b].copy_(attr)
+            ws.attr_i32[:b].copy_(attr)
         if label is not None:
             self.label_buf[:b].copy_(label)
         return b, S
 
-    def _vision_forward(self, b: int, S: int, has_attr: bool, wait=None) -> None:
+    def _vision_forward(self, b: int, S: int, has_attr: bool, wait=None, ws=None) -> None:
+        """Patch embedding -> tower -> ln_post, projection -> logits head.  ws None: on the engine's own buffers and the
+        tower's stash (training, forward()), S_eff and the rank operands refreshed on the way.  ws an `_InferWorkspace`: the
+        same launches on the workspace; whoever calls has refreshed S_eff and the rank operands (infer / inference)."""
         cfg, v = self.cfg, self.cfg.vision
         images = b * S
         P, L = v.grid * v.grid, v.tokens
         rows = images * L
-        a32 = self.attr_i32[:b] if has_attr else None
-        if self.sops.glob:
+        train = ws is None
+        ws = self if train else ws
+        bufs = self.vis if train else ws
+        a32 = ws.attr_i32[:b] if has_attr else None
+        if train and self.sops.glob:
             self._glue(self.sops.prepare)             # S_eff = S + S_global
-        ops.gemm_nt(self.cols[:images * P], self.conv_w, self.patch_out[:images * P], b_packed=self.pk_out.get("conv_w"))
-        ops.embed_lnpre(self.patch_out[:images * P], self.cls, self.pos, self.lnpre[0], self.lnpre[1],
-                        self.vis.x[0][:rows], images, L, rowstat=self.vis.rowp[0] if self.vis.rowp is not None else None)
-        self._rank_operands_ready()                   # LoRA matrices -> GEMM rank operands (they change every step)
-        out = self._stack_forward(self.vis, rows, images, a32, L * S)
-        ops.layernorm_fwd(out, self.hpost[:rows], self.lnpost[0], self.lnpost[1], self.post_stats[0],
-                          self.post_stats[1])
-        ops.gemm_nt(self.hpost[:rows], self.proj_t, self.feat[:rows], b_packed=self.pk_out.get("proj_t"))
+        ops.gemm_nt(ws.cols[:images * P], self.conv_w, ws.patch_out[:images * P], b_packed=self.pk_out.get("conv_w"))
+        lb0 = bufs.layer(0, rows)
+        ops.embed_lnpre(ws.patch_out[:images * P], self.cls, self.pos, self.lnpre[0], self.lnpre[1],
+                        lb0.x, images, L, rowstat=lb0.rowp)
+        if train:
+            self._rank_operands_ready()               # LoRA matrices -> GEMM rank operands (they change every step)
+        out = self._stack_forward(self.vis, rows, images, a32, L * S, bufs)
+        ops.layernorm_fwd(out, ws.hpost[:rows], self.lnpost[0], self.lnpost[1], ws.post_stats[0], ws.post_stats[1])
+        ops.gemm_nt(ws.hpost[:rows], self.proj_t, ws.feat[:rows], b_packed=self.pk_out.get("proj_t"))
         if wait is not None:
             self._ev_wait(torch.cuda.current_stream(self.device), wait)     # text features ready
-        self._head_forward(rows, images, L)
+        self._head_forward(rows, images, L, ws)
 
     def _pack_rank_operands(self) -> None:
         """ffm_lora_pack_multi over every adapter (one or two launches) on the CURRENT stream."""
@@ -1057,14 +1193,15 @@ class FairLoRAEngine:
         else:
             self._ev_wait(torch.cuda.current_stream(self.device), ev)
 
-    def _head_forward(self, rows: int, images: int, L: int) -> None:
+    def _head_forward(self, rows: int, images: int, L: int, ws=None) -> None:
         cfg = self.cfg
+        ws = self if ws is None else ws               # (the text features are the engine's in either case)
         if self.ot:
-            ops.ot_head_fwd(self.feat[:rows], self.tn_buf, self.logit_scale, self.rnorm, self.ot_sim, self.ot_T, self.ot_errs,
-                            self.ot_istop, self.ot_tsum, self.logits_img, images, L, cfg.n_cls, cfg.n_prompts, self.ot,
+            ops.ot_head_fwd(ws.feat[:rows], self.tn_buf, self.logit_scale, ws.rnorm, ws.ot_sim, ws.ot_T, ws.ot_errs,
+                            ws.ot_istop, ws.ot_tsum, ws.logits_img, images, L, cfg.n_cls, cfg.n_prompts, self.ot,
                             cfg.ot_eps, cfg.ot_thresh, cfg.ot_max_iter, cfg.ot_top_percent)
         else:
-            ops.head_fwd(self.feat[:rows], self.tbar_buf, self.logit_scale, self.fbar, self.rnorm, self.logits_img,
+            ops.head_fwd(ws.feat[:rows], self.tbar_buf, self.logit_scale, ws.fbar, ws.rnorm, ws.logits_img,
                          images, L, cfg.n_cls)
 
     def _head_backward(self, rows: int, images: int, L: int) -> None:
@@ -1107,6 +1244,49 @@ class FairLoRAEngine:
         self._text_forward(False)
         self._vision_forward(b, S, attr is not None)
         return self.logits_img[:b * S].view(b, S, -1).mean(1)
+
+    def _infer_prepare(self) -> None:
+        """What an evaluation needs from the CURRENT parameters besides the vision pass: the rank operands of the FairLoRA
+        products, S_eff (GLOBAL_S) and the text features."""
+        self._pack_rank_operands()
+        if self.sops.glob:
+            self.sops.prepare()
+        self._text_forward(False)
+
+    def inference(self):
+        """``with eng.inference():`` - an evaluation session.  On entry the rank operands are packed from the current
+        parameters, S_eff is refreshed and the text tower runs ONCE; inside, `infer` runs the vision tower and the head
+        only.  The session is the contract: the parameters must not be stepped (sgd_step, a captured step, load) inside it -
+        nothing looks for stale operands.  Sessions do not nest usefully (an inner one prepares again)."""
+        eng = self
+
+        class _Session:
+            def __enter__(self):
+                with torch.no_grad():
+                    eng._infer_prepare()
+                self.prev, eng._in_session = eng._in_session, True
+                return eng
+
+            def __exit__(self, *a):
+                eng._in_session = self.prev
+                return False
+        return _Session()
+
+    @torch.no_grad()
+    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
+        """forward()'s logits [B, n_cls], bit for bit, by the forward-only pass: the same launches in the same order on the
+        inference workspace (up to max_infer_images ViT images), with nothing stored for a backward pass - c_fc leaves the
+        activation alone (FFM_EPI_GELU_ONLY), no rank vectors, no log-sum-exp, no LayerNorm statistics.  Gradients,
+        momentum, the training stash, the step-count buffers, the fp16 scale state and a captured training step are not
+        touched.  Outside an `inference()` session every call prepares the rank operands and the text features itself."""
+        if self.sops.type != "FairLoRA":
+            attr = None                               # LoRALinear / SVLoRALinear.forward ignore attr (:241, :307)
+        ws = self.infer_ws
+        b, S = self._load_inputs(image, attr, None, ws)
+        if not self._in_session:
+            self._infer_prepare()
+        self._vision_forward(b, S, attr is not None, ws=ws)
+        return ws.logits_img[:b * S].view(b, S, -1).mean(1)
 
     def _step_body(self, b: int, S: int, has_attr: bool) -> None:
         cfg, v = self.cfg, self.cfg.vision

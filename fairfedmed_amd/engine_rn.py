@@ -504,6 +504,20 @@ class RN50Engine(FairLoRAEngine):
     def buffer_state(self) -> Dict[str, Tensor]:
         return {k: v.clone() for k, v in self.buffer_views().items()}
 
+    # -------------------------------------------------------------- evaluation --
+    # The forward-only pass of the ViT engine (its depth-independent workspace, FFM_EPI_GELU_ONLY) has no RN50 counterpart
+    # yet: `infer` is forward() (eval-mode BatchNorm as there) and a session changes nothing, so that a trainer treats both
+    # engines alike.
+    def _init_infer(self) -> None:
+        self.infer_ws = None
+
+    def inference(self):
+        import contextlib
+        return contextlib.nullcontext(self)
+
+    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
+        return self.forward(image, attr)
+
     # ----------------------------------------------------------------- inputs --
     def _check_batch(self, image: Tensor) -> Tuple[int, int]:
         v = self.cfg.vision

@@ -101,6 +101,16 @@ class CustomCLIP(nn.Module):
         """logits [B, n_cls] (trainers/GLP_OT_SVLoRA.py:677-763, OT='None')."""
         return self.engine.forward(image, attr)
 
+    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
+        """forward()'s logits by the engine's forward-only evaluation pass (FairLoRAEngine.infer): bit-identical, nothing
+        kept for a backward pass, up to the engine's max_infer_images."""
+        return self.engine.infer(image, attr)
+
+    def inference(self):
+        """``with model.inference():`` - an evaluation session (FairLoRAEngine.inference): rank operands and text features
+        are prepared once on entry; the parameters must not be stepped inside it."""
+        return self.engine.inference()
+
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         res = super().load_state_dict(state_dict, strict=strict, assign=False)
         train = set(self.engine.params.keys) | set(buffer_keys(self.cfg))   # live tensors: nothing to rebuild

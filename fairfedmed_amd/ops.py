@@ -176,8 +176,10 @@ def gemm_nt(a: Tensor, b: Tensor, out: Tensor, *, bias=None, ts=None, lw=None, l
             x3: bool = False, rowstats: Optional[Tensor] = None, ln_in: Optional["LnIn"] = None,
             colstats: Optional[Tensor] = None, gelu_deriv: bool = False, bnbwd=None,
             sk_part: Optional[Tensor] = None, lnb_stat: Optional[LnBwdStat] = None,
-            lnb_apply: Optional[LnBwdApply] = None) -> Tensor:
+            lnb_apply: Optional[LnBwdApply] = None, gelu_only: bool = False) -> Tensor:
     """out = epilogue(a @ b.T);  a [M,K], b [N,K], out [M,N] (same dtype).  b_packed: pack_b(b), optional.
+    gelu_only: FFM_EPI_GELU_ONLY - `out` receives quick_gelu(pre) (bit-identical to the `gelu_out` of the two-output call),
+    the pre-activation is not stored and `gelu_out` must be None (the forward-only evaluation pass).
     x3 (float32 operands, at most 64 rows): FFM_F32_X3, the products as bf16 hi/lo pairs on the bf16 matrix cores; with
     `b` in float16: FFM_F32_X3_W16, the same on a weight rounded to IEEE half in memory (half the bytes).
     gelu_deriv (with gelu_out / dgelu_aux): `out` receives / `dgelu_aux` holds quick_gelu'(pre) instead of pre
@@ -215,6 +217,9 @@ def gemm_nt(a: Tensor, b: Tensor, out: Tensor, *, bias=None, ts=None, lw=None, l
             assert extra.dtype == out.dtype and _ld(extra) == _ld(out)
     if res is not None:
         flags |= L.EPI_RESIDUAL
+    if gelu_only:
+        assert gelu_out is None and not gelu_deriv, "gelu_only: the activation goes to `out`, nothing else is stored"
+        flags |= L.EPI_GELU | L.EPI_GELU_ONLY
     if gelu_out is not None:
         flags |= L.EPI_GELU
     if dgelu_aux is not None:

@@ -308,7 +308,8 @@ class GLP_OT_SVLoRA:
     parse_batch_test = _parse
 
     def model_inference(self, input, attr=None):
-        return self.model(input, attr)
+        """Logits of the forward-only evaluation pass (CustomCLIP.infer: bit-identical to self.model(input, attr))."""
+        return self.model.infer(input, attr)
 
     # -------------------------------------------------------------- step --
     def forward_backward(self, batch, is_last_client=False):
@@ -453,12 +454,15 @@ class GLP_OT_SVLoRA:
         auc = 100 * compute_auc; federated_main.py:685-690 indexes [0..3])."""
         self.set_model_mode("eval")
         probs, labels, attrs_all = [], [], []
-        for batch in self.fed_test_loader_x_dict[idx]:
-            image, label, attrs, attr = self.parse_batch_test(batch)
-            logits = self.model_inference(image, attr)
-            probs.append(torch.softmax(logits, -1))
-            labels.append(label)
-            attrs_all.append(attrs)
+        # one evaluation session: the parameters do not move inside a test(), so the rank operands are packed and the text
+        # tower runs once, not per batch
+        with self.model.inference():
+            for batch in self.fed_test_loader_x_dict[idx]:
+                image, label, attrs, attr = self.parse_batch_test(batch)
+                logits = self.model_inference(image, attr)
+                probs.append(torch.softmax(logits, -1))
+                labels.append(label)
+                attrs_all.append(attrs)
         prob_d, y_d = torch.cat(probs).float().contiguous(), torch.cat(labels).contiguous()
         attrs_d = torch.cat(attrs_all, dim=1)                                  # [n_attr, N]
         if prob_d.shape[1] == 2 and not getattr(self.cfg.TEST, "HOST_METRICS", False):

@@ -52,7 +52,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 13  /* 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* ---- epilogue flags for ffm_gemm_nt ------------------------------------ */
@@ -87,6 +87,18 @@ int ffm_abi_version(void);
 #define FFM_EPI_LNB_STAT  2048
 #define FFM_EPI_LNB_APPLY 4096
 
+/* ABI 14: the forward-only evaluation pass (nothing reads QuickGELU's pre-activation without a backward).  Valid only
+ * together with FFM_EPI_GELU: `c` receives quick_gelu(x) and NOTHING ELSE is stored - `c2` is not read, not written and may be
+ * NULL.  x is the value exactly as the two-output epilogue would have stored it (rounded to the storage dtype first), so `c`
+ * here is bit-identical to the `c2` of the same call without the bit.  gelu_deriv must be 0 (FFM_EINVAL otherwise, and
+ * FFM_EINVAL without FFM_EPI_GELU).  Served wherever the vision tower's FFM_EPI_GELU products are served, on the same tile:
+ * the 16-bit panel kernel (BIAS | LORA | GELU | RANKOP, with and without LNIN) and the 128x128 / 128xN kernels (BIAS | GELU,
+ * BIAS | LORA | GELU with and without RANKOP; every dtype, FFM_F32 included).  ffm_gemm_tiles_m / ffm_gemm_tiles_n /
+ * ffm_gemm_tile_shape / ffm_gemm_lgrad_rows answer the same with and without the bit.  The skinny kernels of the text tower
+ * (at most 64 rows) do not have it: such a product runs on the 128x128 kernel under FFM_F32 / FFM_BF16 / FFM_F16 and is
+ * FFM_EUNSUP under FFM_F32_X3 / FFM_F32_X3_W16 (the evaluation pass runs the text tower unchanged, once per session). */
+#define FFM_EPI_GELU_ONLY 8192
+
 typedef struct ffm_gemm_args {
     const void* a;      /* [M, K] dtype, row stride lda (elements) */
     const void* b;      /* [N, K] dtype, row stride ldb: C = A * B^T */
@@ -99,7 +111,7 @@ typedef struct ffm_gemm_args {
     const float* ts;    /* [M, r] fp32: scaling * (xA) * s_b rows (fwd) or scaling * (gB^T) * s_b (bwd) */
     const float* lw;    /* LoRA matrix, [r, N] or (LORA_KR) [N, r], fp32 */
     const void*  res;   /* residual [M, N] dtype, stride ldc */
-    void*        c2;    /* GELU: activated output [M, N] dtype, stride ldc */
+    void*        c2;    /* GELU: activated output [M, N] dtype, stride ldc (GELU_ONLY: not used, may be NULL) */
     const void*  aux;   /* DGELU: pre-activation [M, N] dtype, stride ldc */
     /* FFM_EPI_RANKOP (rank <= 16): t = A . rk^T is accumulated by the GEMM itself (x A forward, g B^T
      * backward), ts = scaling * t * s_b feeds the rank-r update above, `ts` is ignored. */
@@ -384,7 +396,8 @@ int ffm_attnpool_tokens(const void* in, const void* pos, void* out, int B, int H
  * optional causal mask (text tower, clip/model.py:562-568); no dropout.
  * qkv: [B*L, 3*heads*64] rows (b,l) with q|k|v concatenated as nn.MultiheadAttention's
  * packed in-projection produces them (clip/model.py:352).  out: [B*L, heads*64].
- * lse: [B, heads, L] fp32 log-sum-exp of the scaled scores (saved for backward).
+ * lse: [B, heads, L] fp32 log-sum-exp of the scaled scores (saved for backward); NULL: not stored (a forward-only
+ * pass - every kernel behind this entry point skips the store, `out` is the same).
  */
 int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads,
                       int causal, int dtype, void* stream);
