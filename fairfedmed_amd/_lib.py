@@ -55,6 +55,16 @@ class ReduceDesc(C.Structure):
                 ("transpose_r", _i32)]
 
 
+class OptimDesc(C.Structure):
+    """ffm_optim_desc: ten doubles (a float64 tensor of OPTIM_DESC_WORDS elements is its image in device memory)."""
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps", "alpha", "momentum", "weight_decay",
+                                          "pow1", "pow2", "step")]
+
+
+OPTIM_DESC_WORDS = 10
+OPTIM_KINDS = {"sgd": 0, "adam": 1, "adamw": 2, "amsgrad": 3, "rmsprop": 4, "radam": 5}      # FFM_OPTIM_*
+
+
 # name -> argtypes (restype is always int, except the two helpers)
 SIGNATURES = {
     "ffm_abi_version": [],
@@ -125,6 +135,9 @@ SIGNATURES = {
     "ffm_loss_scale": [_vp, _i64, _vp, _vp],
     "ffm_unscale_check": [_vp, _i64, _vp, _vp],
     "ffm_sgd_momentum_gated": [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _i32, _i32, _vp, _vp],
+    "ffm_optim_state_rows": [_i32],
+    "ffm_optim_step": [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
+    "ffm_optim_step_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
     "ffm_scale_by": [_vp, _vp, _vp, _i64, _vp],
     "ffm_scale_acc": [_vp, _vp, _vp, _i64, _vp],
     "ffm_fedavg_finish": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp],

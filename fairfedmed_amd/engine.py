@@ -57,8 +57,23 @@ class FlatParams:
         self.numel = off
         self.flat = torch.zeros(off, device=device, dtype=torch.float32)
         self.grad = torch.zeros(off, device=device, dtype=torch.float32)
-        self.momentum = torch.zeros(off, device=device, dtype=torch.float32)
+        # optimizer state: rows of one [K, numel] tensor (K = ffm_optim_state_rows: 1 for SGD - exactly this allocation -
+        # 2 for adam / adamw / rmsprop / radam, 3 for amsgrad); `momentum` is always the row-0 view
+        self.optim_state = torch.zeros(1, off, device=device, dtype=torch.float32)
+        self.momentum = self.optim_state[0]
+        self.optim_desc: Optional[Tensor] = None      # ffm_optim_desc in device memory (fp16 steps / captured steps)
+        # optimizer applications ATTEMPTED on the host side.  With the device descriptor (fp16, captured steps) an overflowed
+        # step is skipped on the device and optim_desc[9] is the count applied: `steps` is then an upper bound, and
+        # FairLoRAEngine.optim_steps() answers the applied count (SGD only uses `steps == 0` as its first-step flag)
         self.steps = 0
+
+    def set_optim_rows(self, rows: int) -> None:
+        """Give the state tensor `rows` rows for the optimizer chosen; row 0 (momentum) keeps its values."""
+        if rows != self.optim_state.shape[0]:
+            new = torch.zeros(rows, self.numel, device=self.flat.device, dtype=torch.float32)
+            k = min(rows, self.optim_state.shape[0])
+            new[:k].copy_(self.optim_state[:k])
+            self.optim_state, self.momentum = new, new[0]
 
     def view(self, key: str, which: str = "flat") -> Tensor:
         off, shp = self.offsets[key]
@@ -1370,6 +1385,46 @@ class FairLoRAEngine:
             ops.sgd_momentum(p.flat, p.grad, p.momentum, lr, momentum, weight_decay, p.steps == 0, repeats)
         p.steps += repeats
 
+    @torch.no_grad()
+    def optim_step(self, spec, lr: float, repeats: int = 1) -> None:
+        """optim.step() of adam / adamw / amsgrad / rmsprop / radam (fairfedmed_amd.optim.OptimSpec), `repeats` times on the
+        gradients of the last forward_backward at the step numbers steps+1 .. steps+repeats, in one launch.  fp16: gated on the
+        gradient-scale state, with the step count and the running powers in device memory (ffm_optim_step_dev) - on an
+        overflowed step nothing moves but the scale, and the next good step applies the next step number."""
+        p = self.params
+        p.set_optim_rows(spec.rows)
+        if self.scale_state is not None or p.optim_desc is not None:       # (a captured step's counter block stays the truth)
+            self.optim_desc_dev(spec, lr)
+            ops.optim_step_dev(p.flat, p.grad, p.optim_state, spec.kind, p.optim_desc, repeats, self.scale_state)
+        else:
+            ops.optim_step(p.flat, p.grad, p.optim_state, spec.kind, spec.desc(lr, p.steps), repeats)
+        p.steps += repeats
+
+    def optim_desc_dev(self, spec, lr: float) -> Tensor:
+        """The device-resident ffm_optim_desc: created at the host's step count, afterwards only its lr is written."""
+        p = self.params
+        if p.optim_desc is None:
+            p.optim_desc = torch.tensor(spec.desc_values(lr, p.steps), dtype=torch.float64, device=self.device)
+            p.optim_desc_lr = lr
+        elif p.optim_desc_lr != lr:
+            p.optim_desc[0:1].fill_(lr)
+            p.optim_desc_lr = lr
+        return p.optim_desc
+
+    def set_optim_steps(self, spec, lr: float, steps: int) -> None:
+        """Position the optimizer at `steps` applications (a loaded checkpoint, a state handed on by another rank)."""
+        p = self.params
+        p.steps = int(steps)
+        if p.optim_desc is not None:
+            p.optim_desc.copy_(torch.tensor(spec.desc_values(lr, p.steps), dtype=torch.float64))
+            p.optim_desc_lr = lr
+
+    def optim_steps(self) -> int:
+        """Optimizer applications made so far: the device counter where there is one (it does not move on a skipped fp16
+        step; reading it synchronises), the host count otherwise."""
+        p = self.params
+        return int(p.optim_desc[9]) if p.optim_desc is not None else p.steps
+
     def enable_step_counts(self, on: bool = True) -> None:
         """Binary tasks: every training step also leaves ffm_eval_counts(prob, label) in out["counts"] (int64 [2, 10]: the
         integers behind the reference's per-step accuracy / AUC summary, trainers/GLP_OT_SVLoRA.py:959-970), computed on the
@@ -1391,11 +1446,13 @@ class FairLoRAEngine:
 
     # ------------------------------------------------------------- graph --
     def capture_train_step(self, batch_size: int, lr: float, momentum: float, weight_decay: float,
-                           repeats: int = 1) -> "GraphedStep":
+                           repeats: int = 1, optimizer=None) -> "GraphedStep":
         """Capture forward + backward + SGD (all three streams) into one hipGraph.  A step then costs the
         host one graph launch instead of ~450 Python->C calls (the eager loop is host-bound at ~7 ms).  A replay trains
-        as forward_backward + sgd_step(lr, momentum, weight_decay, repeats) does, fp16 gradient-scale gating included."""
-        return GraphedStep(self, batch_size, lr, momentum, weight_decay, repeats)
+        as forward_backward + sgd_step(lr, momentum, weight_decay, repeats) does, fp16 gradient-scale gating included.
+        optimizer: an OptimSpec (fairfedmed_amd.optim) - the body then ends in ffm_optim_step_dev and a replay trains as
+        forward_backward + optim_step(optimizer, lr, repeats) does (momentum / weight_decay come from the spec)."""
+        return GraphedStep(self, batch_size, lr, momentum, weight_decay, repeats, optimizer)
 
     def trainable_state(self) -> Dict[str, Tensor]:
         return {k: self.params.view(k) for k in self.params.keys}
@@ -1406,23 +1463,29 @@ class GraphedStep:
     buffers and replays the graph; results are the engine's usual device tensors (loss, logits, prob, finite)."""
 
     def __init__(self, eng: FairLoRAEngine, batch_size: int, lr: float, momentum: float, weight_decay: float,
-                 repeats: int = 1):
+                 repeats: int = 1, optimizer=None):
         if not 1 <= repeats <= 16:
             raise ValueError(f"repeats must be 1..16, got {repeats}")
         self.eng = eng
         self.repeats = repeats
+        self.spec = optimizer if (optimizer is not None and optimizer.kind != "sgd") else None
         eng.use_replay = False                        # the hipGraph replaces the recorded launch plan
         v, dev = eng.cfg.vision, eng.device
         self.image = torch.zeros(batch_size, 3, v.image_size, v.image_size, device=dev)
         self.attr = torch.zeros(batch_size, device=dev, dtype=torch.int64)
         self.label = torch.zeros(batch_size, device=dev, dtype=torch.int64)
-        self.hp = torch.tensor([lr, momentum, weight_decay], device=dev, dtype=torch.float32)
         p = eng.params
+        # SGD reads {lr, momentum, weight_decay} from hp; an optimizer spec reads the device-resident ffm_optim_desc instead
+        self.hp = torch.tensor([lr, momentum, weight_decay], device=dev, dtype=torch.float32) if self.spec is None else None
+        if self.spec is not None:
+            p.set_optim_rows(self.spec.rows)
         if p.steps == 0:
-            p.momentum.zero_()
+            p.optim_state.zero_()                     # every state row (SGD: the momentum buffer)
         # everything a body writes that outlives a step: the weights, their momentum and gradients, the loss flag and (fp16)
         # the gradient-scale state, which the gated update moves
         live = [p.flat, p.momentum, p.grad, eng.finite] + ([eng.scale_state] if eng.scale_state is not None else [])
+        if self.spec is not None:                     # every state row and the device-resident step count / powers
+            live = [p.flat, p.optim_state, p.grad, eng.finite, eng.optim_desc_dev(self.spec, lr)] + live[4:]
         keep, steps = [t.clone() for t in live], p.steps
 
         def restore():
@@ -1450,11 +1513,18 @@ class GraphedStep:
         with torch.no_grad():
             p = self.eng.params
             # fp16: skipped when the gradients overflowed, then the scale moves (as sgd_step's gated update)
-            ops.sgd_momentum_dev(p.flat, p.grad, p.momentum, self.hp, self.repeats, self.eng.scale_state)
+            if self.spec is not None:
+                ops.optim_step_dev(p.flat, p.grad, p.optim_state, self.spec.kind, p.optim_desc, self.repeats,
+                                   self.eng.scale_state)
+            else:
+                ops.sgd_momentum_dev(p.flat, p.grad, p.momentum, self.hp, self.repeats, self.eng.scale_state)
         return out
 
     def set_lr(self, lr: float) -> None:
-        self.hp[0:1].fill_(lr)
+        if self.spec is not None:
+            self.eng.optim_desc_dev(self.spec, lr)
+        else:
+            self.hp[0:1].fill_(lr)
 
     def run(self, image: Optional[Tensor] = None, attr: Optional[Tensor] = None, label: Optional[Tensor] = None):
         if image is not None:

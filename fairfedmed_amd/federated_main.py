@@ -133,7 +133,11 @@ def setup_cfg(args) -> NS:
         DATALOADER=NS(TRAIN_X=NS(BATCH_SIZE=args.train_batch_size), TEST=NS(BATCH_SIZE=args.test_batch_size), NUM_WORKERS=0),
         MODEL=NS(BACKBONE=NS(NAME="ViT-B/16", PRETRAINED=True), STATE_DICT=None),
         OPTIM=NS(NAME="sgd", LR=args.lr, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, LR_SCHEDULER="single_step",
-                 STEPSIZE=args.stepsize, GAMMA=args.gamma, MAX_EPOCH=1, ROUND=args.round),
+                 STEPSIZE=args.stepsize, GAMMA=args.gamma, MAX_EPOCH=1, ROUND=args.round,
+                 # Dassl's defaults for the other optimizers / schedules (Dassl/dassl/config/defaults.py); a config file's
+                 # OPTIM section overrides them
+                 ADAM_BETA1=0.9, ADAM_BETA2=0.999, RMSPROP_ALPHA=0.99, WARMUP_EPOCH=-1, WARMUP_TYPE="linear",
+                 WARMUP_CONS_LR=1e-5, WARMUP_MIN_LR=1e-5, WARMUP_RECOUNT=True),
         TRAIN=NS(CHECKPOINT_FREQ=0, PRINT_FREQ=10, METRICS_EVERY=1),
         TEST=NS(BATCH_SIZE=args.test_batch_size, NO_TEST=False, EVALUATOR="Classification_oph"),
         TRAINER=NS(NAME=args.trainer, LAMBDA_FAIRNESS=args.lambda_fairness,

@@ -851,6 +851,40 @@ def sgd_momentum_dev(p: Tensor, g: Tensor, buf: Tensor, hp: Tensor, repeats: int
           int(repeats), L.ptr(_f32(state)), L.stream_ptr())
 
 
+def optim_state_rows(kind: str) -> int:
+    """Rows of the [K, numel] optimizer-state tensor (ffm_optim_state_rows): 1 sgd, 3 amsgrad, 2 the others."""
+    return int(L.load().ffm_optim_state_rows(L.OPTIM_KINDS[kind]))
+
+
+def _optim_args(p: Tensor, g: Tensor, state: Tensor, kind: str, scale_state: Optional[Tensor]):
+    _dev(p, g, state, scale_state)
+    if kind not in L.OPTIM_KINDS:
+        raise ValueError(f"unknown optimizer kind {kind!r}")
+    assert state.numel() == optim_state_rows(kind) * p.numel() and g.numel() == p.numel()
+    assert scale_state is None or scale_state.numel() == SCALE_STATE
+    return L.ptr(_f32(p)), L.ptr(_f32(g)), L.ptr(_f32(state)), p.numel(), L.OPTIM_KINDS[kind]
+
+
+def optim_step(p: Tensor, g: Tensor, state: Tensor, kind: str, desc: "L.OptimDesc", repeats: int = 1,
+               scale_state: Optional[Tensor] = None) -> None:
+    """One step of adam / adamw / amsgrad / rmsprop / radam (or sgd), `repeats` times on the same gradient at the step
+    numbers desc.step+1 .. desc.step+repeats, from a host descriptor (ffm_optim_step); the caller advances the descriptor.
+    With the fp16 gradient-scale state it is gated and moves the scale as sgd_momentum_gated does."""
+    import ctypes
+    a = _optim_args(p, g, state, kind, scale_state)
+    _call("ffm_optim_step", *a, ctypes.addressof(desc), int(repeats), L.ptr(_f32(scale_state)), L.stream_ptr())
+
+
+def optim_step_dev(p: Tensor, g: Tensor, state: Tensor, kind: str, desc_dev: Tensor, repeats: int = 1,
+                   scale_state: Optional[Tensor] = None) -> None:
+    """optim_step with the descriptor in device memory (a float64 tensor of _lib.OPTIM_DESC_WORDS elements) - the step
+    count and the running powers advance there, and not at all on a skipped step (ffm_optim_step_dev)."""
+    _dev(desc_dev)
+    assert desc_dev.dtype == torch.float64 and desc_dev.numel() == L.OPTIM_DESC_WORDS and desc_dev.is_contiguous()
+    a = _optim_args(p, g, state, kind, scale_state)
+    _call("ffm_optim_step_dev", *a, L.ptr(desc_dev), int(repeats), L.ptr(_f32(scale_state)), L.stream_ptr())
+
+
 def scale_by(p: Tensor, w: Tensor, out: Tensor) -> None:
     _dev(p, w, out)
     _call("ffm_scale_by", L.ptr(_f32(p)), L.ptr(_f32(w)), L.ptr(_f32(out)), p.numel(), L.stream_ptr())

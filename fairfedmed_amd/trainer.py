@@ -28,6 +28,7 @@ from . import ops
 from .metrics import (auc_macro_ovr, basic_from_counts, comprehensive_scores, comprehensive_scores_from_counts,
                       macro_f1)
 from .model import CustomCLIP
+from .optim import build_lr_schedule, build_optim_spec
 from .registry import TRAINER_REGISTRY
 
 ATTRIBUTE_GROUPS = {   # trainers/GLP_OT_SVLoRA.py:775-790
@@ -230,11 +231,14 @@ class GLP_OT_SVLoRA:
         if not getattr(tc, "HOST_METRICS", False) and getattr(cfg.TRAINER, "LAMBDA_FAIRNESS", 0.0) == 0.0:
             self.engine.enable_step_counts()
         self._finite_acc = torch.ones(1, device=self.device, dtype=torch.int32)
+        # Dassl/dassl/optim/optimizer.py:13-142 and lr_scheduler.py:83-155: OPTIM.NAME picks the update rule, OPTIM.LR_SCHEDULER
+        # (+ WARMUP_*) the schedule; a config without those keys is sgd / single_step / no warm-up
         o = cfg.OPTIM
+        self.optim_spec = build_optim_spec(o)
         self.optim = NS(lr0=o.LR, momentum=o.MOMENTUM, weight_decay=o.WEIGHT_DECAY,
                         param_groups=[{"lr": o.LR}])
-        stepsize = o.STEPSIZE[-1] if isinstance(o.STEPSIZE, (list, tuple)) else o.STEPSIZE
-        self.sched = NS(step_size=stepsize if stepsize > 0 else o.MAX_EPOCH, gamma=o.GAMMA, last_epoch=0)
+        self.sched = build_lr_schedule(self.optim.param_groups[0], o)
+        self.engine.params.set_optim_rows(self.optim_spec.rows)
         # trainers/GLP_OT_SVLoRA.py:866-870: BOTH names are registered with the SAME optimizer and scheduler objects
         # when UNFREEZE_IMAGE_ENCODER is set (every FairLoRA script sets it)
         self.register_model("prompt_learner", self.model.prompt_learner, self.optim, self.sched)
@@ -265,34 +269,34 @@ class GLP_OT_SVLoRA:
         return sum(1 for n in self.get_model_names(names) if self._optims[n] is not None)
 
     def update_lr(self, names=None):
-        """StepLR.step() (Dassl/dassl/optim/lr_scheduler.py:100-115) at the end of a local epoch, once per registered
+        """scheduler.step() (Dassl/dassl/optim/lr_scheduler.py:83-155) at the end of a local epoch, once per registered
         name that carries the (shared) scheduler."""
-        s = self.sched
-        s.last_epoch += self.steps_per_update(names)
-        self.optim.param_groups[0]["lr"] = self.optim.lr0 * s.gamma ** (s.last_epoch // s.step_size)
+        for _ in range(self.steps_per_update(names)):
+            self.sched.step()
 
     def set_lr_epoch(self, last_epoch: int) -> None:
-        """Position the (shared) StepLR as if `last_epoch` scheduler steps had been taken: the rank-parallel round loop
+        """Position the (shared) scheduler as if `last_epoch` scheduler steps had been taken: the rank-parallel round loop
         calls this with the global count of client-epochs, so the schedule is the reference's whatever the world size."""
-        s = self.sched
-        s.last_epoch = int(last_epoch)
-        self.optim.param_groups[0]["lr"] = self.optim.lr0 * s.gamma ** (s.last_epoch // s.step_size)
+        self.sched.set_lr_epoch(last_epoch)
 
     def optimizer_state(self):
-        """(momentum buffers fp32 [numel] on the device, [SGD steps taken, StepLR.last_epoch, lr] float64 on the same
-        device): what the reference's single shared optimizer / scheduler carries from one client to the next."""
+        """(optimizer state rows fp32 [K * numel] on the device - for sgd the momentum buffers [numel] -, [optimizer steps
+        taken, scheduler steps taken, lr] float64 on the same device): what the reference's single shared optimizer /
+        scheduler carries from one client to the next."""
         p = self.engine.params
-        scal = torch.tensor([p.steps, self.sched.last_epoch, self.optim.param_groups[0]["lr"]], dtype=torch.float64,
+        steps = p.steps if self.optim_spec.kind == "sgd" else self.engine.optim_steps()
+        scal = torch.tensor([steps, self.sched.last_epoch, self.optim.param_groups[0]["lr"]], dtype=torch.float64,
                             device=p.momentum.device)
-        return p.momentum, scal
+        return p.optim_state.view(-1), scal
 
     def load_optimizer_state(self, momentum: torch.Tensor, scal: torch.Tensor) -> None:
         p = self.engine.params
         if momentum.data_ptr() != p.momentum.data_ptr():
-            p.momentum.copy_(momentum)
+            p.optim_state.view(-1).copy_(momentum)
         steps, last_epoch, lr = scal.cpu().tolist()
-        p.steps, self.sched.last_epoch = int(steps), int(last_epoch)
+        self.sched.set_lr_epoch(int(last_epoch))
         self.optim.param_groups[0]["lr"] = lr
+        self.engine.set_optim_steps(self.optim_spec, lr, int(steps))
 
     # ------------------------------------------------------------- batch --
     def _parse(self, batch):
@@ -324,8 +328,11 @@ class GLP_OT_SVLoRA:
         # no fairness term (trainers/GLP_OT_SVLoRA.py:890-898); autocast itself is not mirrored (fp32)
         amp = self.cfg.TRAINER.GLP_OT.PREC == "amp"
         out = self.engine.forward_backward(image, None if amp else attr, label)
-        self.engine.sgd_step(self.get_current_lr(), self.optim.momentum, self.optim.weight_decay,
-                             repeats=1 if amp else self.steps_per_update())     # amp: scaler.step(optim) once (:896)
+        repeats = 1 if amp else self.steps_per_update()                     # amp: scaler.step(optim) once (:896)
+        if self.optim_spec.kind == "sgd":
+            self.engine.sgd_step(self.get_current_lr(), self.optim.momentum, self.optim.weight_decay, repeats=repeats)
+        else:
+            self.engine.optim_step(self.optim_spec, self.get_current_lr(), repeats=repeats)
         train_cfg = getattr(self.cfg, "TRAIN", NS())
         every = getattr(train_cfg, "METRICS_EVERY", 1)
         summary = {}
@@ -438,6 +445,16 @@ class GLP_OT_SVLoRA:
             frozen_changed |= any(f"{name}.{k}" not in train for k in sd)
         if frozen_changed:                                            # rebuild the compute-dtype copies of frozen tensors
             self.engine.load_frozen(self.model.state_dict())
+        # the shared optimizer / scheduler state save_model wrote (every state row, the step counts, the lr), so that
+        # training goes on from the checkpoint as it would have without the round trip; a checkpoint of another
+        # optimizer (a different number of state rows) brings its weights only
+        opt = ckpt.get("optimizer")
+        if opt is not None and opt["momentum"].numel() == self.engine.params.optim_state.numel():
+            self.load_optimizer_state(opt["momentum"].to(self.device), opt["scalars"])
+        elif opt is not None:
+            print("Optimizer state of the checkpoint ({} values) does not fit OPTIM.NAME = {} ({} values): weights loaded, "
+                  "optimizer and scheduler start afresh".format(opt["momentum"].numel(), self.optim_spec.kind,
+                                                                self.engine.params.optim_state.numel()))
 
     def fed_before_train(self, is_global=False):
         self.start_epoch = 0

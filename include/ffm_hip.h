@@ -52,7 +52,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* ---- epilogue flags for ffm_gemm_nt ------------------------------------ */
@@ -638,6 +638,55 @@ int ffm_sgd_momentum_gated(float* p, const float* g, float* buf, int64_t n, floa
  * above: the update is skipped when ok == 0 and the scale then moves, exactly as in ffm_sgd_momentum_gated (ABI 13). */
 int ffm_sgd_momentum_dev(float* p, const float* g, float* buf, int64_t n, const float* hp, int repeats, float* state,
                          void* stream);
+
+/*
+ * The other optimizers build_optimizer can construct (Dassl/dassl/optim/optimizer.py:88-138), one launch over the flat
+ * buffer per optimizer step, `repeats` (1..16) applications on the SAME gradient at the consecutive step numbers
+ * t+1 .. t+repeats, each with its own bias corrections (Dassl/dassl/engine/trainer.py:333-337 steps the shared optimizer
+ * once per registered name):
+ *   FFM_OPTIM_ADAM / _AMSGRAD  torch.optim.Adam (optimizer.py:88-103): L2 decay folded into the gradient, bias
+ *                              corrections; amsgrad keeps the running maximum of the second moment
+ *   FFM_OPTIM_ADAMW            torch.optim.AdamW (optimizer.py:132-138): p *= 1 - lr*wd, then Adam without L2
+ *   FFM_OPTIM_RMSPROP          torch.optim.RMSprop(momentum, alpha), not centered (optimizer.py:115-122)
+ *   FFM_OPTIM_RADAM            Dassl/dassl/optim/radam.py:18-130 (optimizer.py:124-130): rectified above N_sma = 5,
+ *                              degenerated_to_sgd below; p += -wd*lr*p before the update
+ *   FFM_OPTIM_SGD              the ffm_sgd_momentum_n update (first_step when step == 0), for completeness
+ * state is [K][n] fp32, K = ffm_optim_state_rows(kind): row 0 the first moment (rmsprop / sgd: the momentum buffer), row 1
+ * the second moment (rmsprop: the square average), row 2 amsgrad's running maximum; all zero before the first step.
+ * ffm_optim_desc holds everything else, in double: the hyper-parameters as the Python values (1 - beta is formed in
+ * double and then rounded to float, as torch does), the count t of applications made so far and the running products
+ * pow1 = beta1^t, pow2 = beta2^t (1.0 at t = 0), advanced by ONE multiplication per application - never by pow() - so
+ * that a host and a device that start from the same values stay bit-identical.
+ */
+#define FFM_OPTIM_SGD 0
+#define FFM_OPTIM_ADAM 1
+#define FFM_OPTIM_ADAMW 2
+#define FFM_OPTIM_AMSGRAD 3
+#define FFM_OPTIM_RMSPROP 4
+#define FFM_OPTIM_RADAM 5
+
+typedef struct ffm_optim_desc {
+    double lr, beta1, beta2, eps, alpha, momentum, weight_decay;
+    double pow1, pow2;   /* beta1^step, beta2^step as running products */
+    double step;         /* applications made so far (an integer value) */
+} ffm_optim_desc;
+
+/* rows of `state`: 1 sgd, 2 adam / adamw / rmsprop / radam, 3 amsgrad; FFM_EINVAL for an unknown kind */
+int ffm_optim_state_rows(int kind);
+
+/* One optimizer step from a HOST descriptor (read during the call; the caller advances step / pow1 / pow2 by `repeats`
+ * afterwards).  scale_state (may be NULL) is the fp16 gradient-scale state of ffm_loss_scale: the update is skipped when
+ * ok == 0 and the scale then moves, exactly as in ffm_sgd_momentum_gated - a caller that cannot know whether the step was
+ * skipped keeps its count on the device (ffm_optim_step_dev).  Replaces optim.step() of model_update
+ * (Dassl/dassl/engine/trainer.py:333-337) for every OPTIM.NAME but sgd. */
+int ffm_optim_step(float* p, const float* g, float* state, int64_t n, int kind, const ffm_optim_desc* desc, int repeats,
+                   float* scale_state, void* stream);
+
+/* The same update with the descriptor in DEVICE memory, for a captured graph (as ffm_sgd_momentum_dev): a small launch
+ * behind the update advances step / pow1 / pow2 by `repeats` there - nothing on a skipped step, so the next good step
+ * applies step number t+1 - and the scale moves behind that. */
+int ffm_optim_step_dev(float* p, const float* g, float* state, int64_t n, int kind, ffm_optim_desc* desc_dev, int repeats,
+                       float* scale_state, void* stream);
 
 /*
  * Round boundary helpers (utils/fed_utils.py:42-100) on the flat trainable
