@@ -124,6 +124,7 @@ SIGNATURES = {
     "ffm_reduce_partials_multi": [_vp, _i32, _i32, _vp],
     "ffm_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_ce_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "ffm_ce_fair_loss": [_vp] * 10 + [_i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "ffm_head_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_text_embed": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_text_tail_fwd": [_vp] * 10 + [_i32] * 4 + [_vp],

@@ -133,6 +133,133 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
     }
 }
 
+// ce_loss_kernel plus the group-confidence-gap term (trainers/GLP_OT_SVLoRA.py:928-948; formulas: include/ffm_hip.h).
+// Pass 1 is ce_loss_kernel's loop, operation for operation (logits and prob come out bit-identical), and also sums
+// c_b = p[b][y_b] and the sample count per group; one shared-memory tree reduces the CE sum and the 2 G group sums
+// together (fixed order); every thread then forms m_g, M, F and kappa_g from the totals, and pass 2 writes dlogits.
+constexpr int HD_MAXG = FFM_MAX_GROUPS;
+
+__global__ __launch_bounds__(256) void ce_fair_loss_kernel(const float* __restrict__ logits_img,
+                                                           const int64_t* __restrict__ label,
+                                                           const int32_t* __restrict__ attr, float* __restrict__ logits,
+                                                           float* __restrict__ prob, float* __restrict__ loss,
+                                                           float* __restrict__ terms, float* __restrict__ gstat,
+                                                           float* __restrict__ dlogits_img, int32_t* __restrict__ finite,
+                                                           int nb, int S, int n_cls, int G, float lambda, int with_grad) {
+    __shared__ float part[HD_MAXG + 1][256];        // row 0: CE, row 1 + g: sum of c_b over group g
+    __shared__ int cnt[HD_MAXG][256];               // samples of group g
+    float my = 0.f, cs[HD_MAXG];
+    int cn[HD_MAXG];
+#pragma unroll
+    for (int g = 0; g < HD_MAXG; ++g) { cs[g] = 0.f; cn[g] = 0; }
+    for (int b = threadIdx.x; b < nb; b += 256) {
+        float lg[HD_MAXC];
+        float mx = -INFINITY;
+        for (int c = 0; c < n_cls; ++c) {
+            float s = 0.f;
+            for (int k = 0; k < S; ++k) s += logits_img[((size_t)b * S + k) * n_cls + c];
+            lg[c] = s / (float)S;
+            logits[(size_t)b * n_cls + c] = lg[c];
+            mx = fmaxf(mx, lg[c]);
+        }
+        float se = 0.f;
+        for (int c = 0; c < n_cls; ++c) se += expf(lg[c] - mx);
+        const float lse = mx + logf(se);
+        const int y = (int)label[b];
+        my += lse - lg[y];
+        float cb = 0.f;
+        for (int c = 0; c < n_cls; ++c) {
+            const float pc = expf(lg[c] - lse);
+            prob[(size_t)b * n_cls + c] = pc;
+            cb = c == y ? pc : cb;
+        }
+        const int a = attr[b];
+#pragma unroll
+        for (int g = 0; g < HD_MAXG; ++g) {
+            const bool in = a == g && g < G;
+            cs[g] += in ? cb : 0.f;
+            cn[g] += in ? 1 : 0;
+        }
+    }
+    part[0][threadIdx.x] = my;
+#pragma unroll
+    for (int g = 0; g < HD_MAXG; ++g) { part[1 + g][threadIdx.x] = cs[g]; cnt[g][threadIdx.x] = cn[g]; }
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+            part[0][threadIdx.x] += part[0][threadIdx.x + o];
+            for (int g = 0; g < G; ++g) {
+                part[1 + g][threadIdx.x] += part[1 + g][threadIdx.x + o];
+                cnt[g][threadIdx.x] += cnt[g][threadIdx.x + o];
+            }
+        }
+        __syncthreads();
+    }
+    // the statistics, redundantly in every thread from the same totals in the same order (groups ascending)
+    float m[HD_MAXG], kap[HD_MAXG];
+    int P = 0;
+    float M = 0.f;
+#pragma unroll
+    for (int g = 0; g < HD_MAXG; ++g) {
+        const int n = g < G ? cnt[g][0] : 0;
+        m[g] = n > 0 ? 1.f - part[1 + g][0] / (float)n : 0.f;
+        if (n > 0) { M += m[g]; ++P; }
+    }
+    float F = 0.f, sbar = 0.f;
+    if (P > 0) M /= (float)P;
+#pragma unroll
+    for (int g = 0; g < HD_MAXG; ++g) {
+        const bool here = g < G && cnt[g][0] > 0;
+        const float d = m[g] - M;
+        if (here) { F += fabsf(d); sbar += d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f; }
+    }
+    if (P > 0) { F /= (float)P; sbar /= (float)P; }
+    if (P <= 1) F = 0.f;
+#pragma unroll
+    for (int g = 0; g < HD_MAXG; ++g) {
+        const int n = g < G ? cnt[g][0] : 0;
+        const float d = m[g] - M;
+        const float sg = d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f;
+        kap[g] = (n > 0 && P > 1) ? -(sg - sbar) / ((float)P * (float)n) : 0.f;
+    }
+    if (threadIdx.x == 0) {
+        const float cls = part[0][0] / (float)nb;
+        const float l = cls + lambda * F;
+        terms[0] = cls;
+        terms[1] = F;
+        loss[0] = l;
+        if (finite) finite[0] = isfinite(l) ? 1 : 0;
+        if (gstat) {
+#pragma unroll
+            for (int g = 0; g < HD_MAXG; ++g) {
+                if (g < G) {
+                    gstat[2 * g] = m[g];
+                    gstat[2 * g + 1] = (float)cnt[g][0];
+                }
+            }
+        }
+    }
+    // pass 2: each thread reads back the prob rows it wrote itself
+    const float wl = with_grad ? lambda : 0.f;
+    for (int b = threadIdx.x; b < nb; b += 256) {
+        const int y = (int)label[b];
+        const int a = attr[b];
+        float kb = 0.f;
+#pragma unroll
+        for (int g = 0; g < HD_MAXG; ++g) kb = a == g ? kap[g] : kb;
+        float cb = 0.f;
+        for (int c = 0; c < n_cls; ++c) cb = c == y ? prob[(size_t)b * n_cls + c] : cb;
+        const float e = wl * kb * cb;
+        for (int c = 0; c < n_cls; ++c) {
+            const float pc = prob[(size_t)b * n_cls + c];
+            const float t = c == y ? 1.f : 0.f;
+            // (e == 0: ce_loss_kernel's expression, so its bits)
+            const float dl = e == 0.f ? (pc - t) / (float)nb / (float)S : ((pc - t) / (float)nb + e * (t - pc)) / (float)S;
+            for (int k = 0; k < S; ++k) dlogits_img[((size_t)b * S + k) * n_cls + c] = dl;
+        }
+    }
+}
+
 // dfbar[b] = e^ls * sum_c dlogits[b][c] tbar[c];  y = f*rn;  df = (dy - y <y,dy>) rn, dy = dfbar/(L-1)
 template <typename T>
 __global__ __launch_bounds__(64 * HD_NW) void head_bwd_kernel(const T* __restrict__ f, const float* __restrict__ tbar,
@@ -236,6 +363,18 @@ extern "C" int ffm_ce_loss(const float* logits_img, const int64_t* label, float*
     if (nb <= 0 || S <= 0 || n_cls <= 0 || n_cls > HD_MAXC) return FFM_EINVAL;
     hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits_img, label, logits, prob,
                        loss, dlogits_img, finite_flag, nb, S, n_cls);
+    FFM_CHECK_LAUNCH();
+    return FFM_OK;
+}
+
+extern "C" int ffm_ce_fair_loss(const float* logits_img, const int64_t* label, const int32_t* attr, float* logits,
+                                float* prob, float* loss, float* terms, float* gstat, float* dlogits_img,
+                                int32_t* finite_flag, int nb, int S, int n_cls, int G, float lambda, int with_grad,
+                                void* stream) {
+    if (!logits_img || !label || !attr || !logits || !prob || !loss || !terms || !dlogits_img) return FFM_EINVAL;
+    if (nb <= 0 || S <= 0 || n_cls <= 0 || n_cls > HD_MAXC || G <= 0 || G > FFM_MAX_GROUPS) return FFM_EINVAL;
+    hipLaunchKernelGGL(ce_fair_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits_img, label, attr, logits,
+                       prob, loss, terms, gstat, dlogits_img, finite_flag, nb, S, n_cls, G, lambda, with_grad ? 1 : 0);
     FFM_CHECK_LAUNCH();
     return FFM_OK;
 }

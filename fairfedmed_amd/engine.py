@@ -499,6 +499,10 @@ class FairLoRAEngine:
         self.attr_i32 = torch.zeros(max_images, device=dev, dtype=torch.int32)
         self.label_buf = torch.zeros(max_images, device=dev, dtype=torch.int64)
         self._counts_buf = None                       # enable_step_counts()
+        # set_fairness(): lambda and with_grad of the loss's group-confidence-gap term; {cls, F} and {m_g, n_g} per group
+        self._fair_lam, self._fair_grad, self._fair_step = 0.0, False, False
+        self.loss_terms = torch.zeros(2, device=dev, dtype=f32)
+        self.group_conf = torch.zeros(ops.MAX_GROUPS, 2, device=dev, dtype=f32)
         self.tbar_buf = torch.zeros(cfg.n_cls, v.out_dim, device=dev, dtype=f32)
         self.ot = cfg.ot if cfg.ot != "None" else None
         if self.ot:
@@ -1321,8 +1325,15 @@ class FairLoRAEngine:
             self._vision_forward(b, S, has_attr, wait=self.ev_text_fwd)
         finally:
             self._pack_event = None
-        ops.ce_loss(self.logits_img, self.label_buf, self.logits, self.prob, self.loss, self.dlogits_img,
-                    self.finite, b, S, cfg.n_cls)
+        if self._fair_step:
+            # set_fairness: CE + lambda * the confidence gap between the groups of the batch (attr_i32: one entry per sample /
+            # volume, loaded for the loss even where the adapters take no attribute)
+            ops.ce_fair_loss(self.logits_img, self.label_buf, self.attr_i32, self.logits, self.prob, self.loss,
+                             self.loss_terms, self.group_conf, self.dlogits_img, self.finite, b, S, cfg.n_cls,
+                             self._fair_groups(), self._fair_lam, self._fair_grad)
+        else:
+            ops.ce_loss(self.logits_img, self.label_buf, self.logits, self.prob, self.loss, self.dlogits_img,
+                        self.finite, b, S, cfg.n_cls)
         if self.scale_state is not None:
             ops.loss_scale(self.dlogits_img[:b * S], self.scale_state)
         self._head_backward(rows, images, L)
@@ -1341,12 +1352,19 @@ class FairLoRAEngine:
     def forward_backward(self, image: Tensor, attr: Optional[Tensor], label: Tensor) -> Dict[str, Tensor]:
         """Forward, CE loss, backward; gradients of every trainable tensor land in params.grad.
         Returns device tensors (no host sync): loss [1], logits [B,n_cls], prob [B,n_cls], finite [1].
-        The first call for a batch shape records the step's launch plan; later calls replay it."""
+        The first call for a batch shape records the step's launch plan; later calls replay it.
+        After set_fairness(lam != 0) and with an attribute, loss is CE + lam * F and the result also carries loss_terms [2] =
+        {CE, F} and group_conf [G, 2] = {m_g, n_g}; without an attribute there is no term (as in the reference)."""
+        # the loss's term reads the attribute for every adapter type (the reference applies it to LoRA / SVLoRA runs too,
+        # trainers/GLP_OT_SVLoRA.py:928-948); the rank products of those types still run without one
+        fair = self._fair_lam != 0.0 and attr is not None
+        loss_attr = attr if fair else None
         if self.sops.type != "FairLoRA":
             attr = None
         with torch.no_grad():
-            b, S = self._load_inputs(image, attr, label)
-            key = (b, S, attr is not None, torch.cuda.current_stream(self.device).cuda_stream)
+            b, S = self._load_inputs(image, attr if attr is not None else loss_attr, label)
+            key = (b, S, attr is not None, torch.cuda.current_stream(self.device).cuda_stream) + (("fair",) if fair else ())
+            self._fair_step = fair
             plan = self.step_plans.get(key) if self.use_replay else None
             if plan is not None:
                 for f in plan:
@@ -1373,6 +1391,8 @@ class FairLoRAEngine:
         out = {"loss": self.loss, "logits": self.logits[:b], "prob": self.prob[:b], "finite": self.finite}
         if self._counts_buf is not None:
             out["counts"] = self._counts_buf          # ffm_eval_counts of (prob, label): rows {unknown, all}
+        if fair:
+            out["loss_terms"], out["group_conf"] = self.loss_terms, self.group_conf[:self._fair_groups()]
         return out
 
     @torch.no_grad()
@@ -1434,6 +1454,24 @@ class FairLoRAEngine:
             self._counts_buf = torch.zeros(2, ops.EVAL_SLOTS, device=self.device, dtype=torch.int64) if want else None
             self.step_plans.clear()
 
+    def set_fairness(self, lam: float, with_grad: bool = False) -> None:
+        """TRAINER.LAMBDA_FAIRNESS on the device: with lam != 0 a training step that is given an attribute computes its loss
+        with ffm_ce_fair_loss - CE + lam * F, F the mean absolute deviation of the groups' mean (1 - p[label]) over the groups
+        present in the batch (trainers/GLP_OT_SVLoRA.py:928-948) - for every adapter type; lam == 0 is ffm_ce_loss and
+        today's plans.  with_grad False (default) is the reference: the term is built from detached values and moves the
+        reported loss only.  with_grad True is an extension beyond the reference: the term's gradient joins dloss/dlogits
+        and training changes.  Both scalars are baked into recorded launches, so the plans are dropped here, and a
+        captured step (capture_train_step) keeps the values it was captured with: call this BEFORE the capture."""
+        lam, with_grad = float(lam), bool(with_grad)
+        if (lam, with_grad) != (self._fair_lam, self._fair_grad):
+            self._fair_lam, self._fair_grad = lam, with_grad
+            self.step_plans.clear()
+
+    def _fair_groups(self) -> int:
+        """Groups the loss's term looks for: the adapters' for FairLoRA (an attribute beyond them could not pass through
+        FairLoRALinear), every index the library knows for the types that carry no groups (num_groups is 1 there)."""
+        return self.cfg.lora.num_groups if self.sops.type == "FairLoRA" else ops.MAX_GROUPS
+
     def set_overlap(self, on: bool) -> None:
         """on: text tower and LoRA-gradient reductions run on their own streams beside the vision chain
         (default).  off: everything on the caller's stream, one kernel at a time (clean per-kernel timings)."""
@@ -1447,7 +1485,8 @@ class FairLoRAEngine:
     # ------------------------------------------------------------- graph --
     def capture_train_step(self, batch_size: int, lr: float, momentum: float, weight_decay: float,
                            repeats: int = 1, optimizer=None) -> "GraphedStep":
-        """Capture forward + backward + SGD (all three streams) into one hipGraph.  A step then costs the
+        """Capture forward + backward + SGD (all three streams) into one hipGraph.  set_fairness must precede the capture
+        (the loss kernel and its scalars are part of the graph).  A step then costs the
         host one graph launch instead of ~450 Python->C calls (the eager loop is host-bound at ~7 ms).  A replay trains
         as forward_backward + sgd_step(lr, momentum, weight_decay, repeats) does, fp16 gradient-scale gating included.
         optimizer: an OptimSpec (fairfedmed_amd.optim) - the body then ends in ffm_optim_step_dev and a replay trains as

@@ -72,6 +72,8 @@ def build_parser() -> argparse.ArgumentParser:
     a("--shared_half_s", type=bool, default=False)
     a("--lora_global_s", type=bool, default=False)
     a("--lambda_fairness", type=float, default=0.0)
+    a("--fairness_grad", action="store_true",
+      help="let the --lambda_fairness term reach the gradients (an extension: the reference detaches it, which is the default)")
     a("--idxs_users_train", type=list, default=[])
     a("--idxs_users_test", type=list, default=[])
     a("--disable_attr", action="store_true")
@@ -140,7 +142,7 @@ def setup_cfg(args) -> NS:
                  WARMUP_CONS_LR=1e-5, WARMUP_MIN_LR=1e-5, WARMUP_RECOUNT=True),
         TRAIN=NS(CHECKPOINT_FREQ=0, PRINT_FREQ=10, METRICS_EVERY=1),
         TEST=NS(BATCH_SIZE=args.test_batch_size, NO_TEST=False, EVALUATOR="Classification_oph"),
-        TRAINER=NS(NAME=args.trainer, LAMBDA_FAIRNESS=args.lambda_fairness,
+        TRAINER=NS(NAME=args.trainer, LAMBDA_FAIRNESS=args.lambda_fairness, FAIRNESS_GRAD=args.fairness_grad,
                    GLP_OT=NS(N_CTX=args.n_ctx, CSC=False, CTX_INIT=args.ctx_init, PREC=args.prec,
                              CLASS_TOKEN_POSITION="end", N=args.num_prompt, THRESH=args.thresh, EPS=args.eps, OT=args.OT,
                              TOP_PERCENT=args.top_percent, MAX_ITER=args.max_iter),

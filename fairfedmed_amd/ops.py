@@ -793,6 +793,22 @@ def ce_loss(logits_img: Tensor, label: Tensor, logits: Tensor, prob: Tensor, los
                                  L.stream_ptr())
 
 
+def ce_fair_loss(logits_img: Tensor, label: Tensor, attr: Tensor, logits: Tensor, prob: Tensor, loss: Tensor,
+                 terms: Tensor, gstat: Optional[Tensor], dlogits_img: Tensor, finite: Optional[Tensor], nb: int, S: int,
+                 n_cls: int, G: int, lam: float, with_grad: bool = False) -> None:
+    """ce_loss plus lam * the group-confidence-gap term (ffm_ce_fair_loss): loss [1] = terms[0] + lam * terms[1], terms [2]
+    = {cls, F}, gstat [G, 2] = {m_g, n_g} (optional); attr [>= nb] int32, one entry per sample.  with_grad: dlogits_img also
+    carries the term's gradient (an extension; off, it is ce_loss's bit for bit, as the reference detaches the term)."""
+    _dev(logits_img, label, attr, logits, prob, loss, terms, gstat, dlogits_img, finite)
+    assert label.dtype == torch.int64 and attr.dtype == torch.int32 and (finite is None or finite.dtype == torch.int32)
+    assert attr.is_contiguous() and attr.numel() >= nb and label.numel() >= nb and terms.numel() >= 2
+    assert logits_img.numel() >= nb * S * n_cls and dlogits_img.numel() >= nb * S * n_cls
+    assert logits.numel() >= nb * n_cls and prob.numel() >= nb * n_cls and (gstat is None or gstat.numel() >= 2 * G)
+    _call("ffm_ce_fair_loss", L.ptr(_f32(logits_img)), L.ptr(label), L.ptr(attr), L.ptr(_f32(logits)), L.ptr(_f32(prob)),
+          L.ptr(_f32(loss)), L.ptr(_f32(terms)), L.ptr(_f32(gstat)), L.ptr(_f32(dlogits_img)), L.ptr(finite), nb, S,
+          n_cls, G, float(lam), int(bool(with_grad)), L.stream_ptr())
+
+
 def head_bwd(f: Tensor, tbar: Tensor, logit_scale: Tensor, fbar: Tensor, rnorm: Tensor, dlogits_img: Tensor,
              df: Tensor, dtbar: Tensor, B: int, Ltok: int, n_cls: int) -> None:
     _dev(f, tbar, logit_scale, fbar, rnorm, dlogits_img, df, dtbar)
@@ -816,6 +832,7 @@ def sgd_momentum(p: Tensor, g: Tensor, buf: Tensor, lr: float, momentum: float, 
               weight_decay, int(first_step), int(repeats), L.stream_ptr())
 
 
+MAX_GROUPS = 8      # FFM_MAX_GROUPS (include/ffm_hip.h)
 SCALE_STATE = 8     # floats of the fp16 gradient-scale state (include/ffm_hip.h: ffm_loss_scale)
 
 

@@ -226,10 +226,13 @@ class GLP_OT_SVLoRA:
         self.model = CustomCLIP(mcfg, sd, dtype=dtype, max_images=bs, device=str(self.device))
         self.engine = self.model.engine
         # the per-step summary's evaluator counts ride inside the step, beside the backward pass (binary tasks, device
-        # metrics: the default); TRAIN.HOST_METRICS / a fairness term keep the host path, which does not read them
+        # metrics: the default); TRAIN.HOST_METRICS keeps the host path, which does not read them
         tc = getattr(cfg, "TRAIN", NS())
-        if not getattr(tc, "HOST_METRICS", False) and getattr(cfg.TRAINER, "LAMBDA_FAIRNESS", 0.0) == 0.0:
+        if not getattr(tc, "HOST_METRICS", False):
             self.engine.enable_step_counts()
+        # TRAINER.LAMBDA_FAIRNESS: the loss's group-confidence-gap term is part of the step's loss kernel (ffm_ce_fair_loss);
+        # TRAINER.FAIRNESS_GRAD (--fairness_grad) lets it reach the gradients - off, it is the reference's detached term
+        self.engine.set_fairness(getattr(cfg.TRAINER, "LAMBDA_FAIRNESS", 0.0), getattr(cfg.TRAINER, "FAIRNESS_GRAD", False))
         self._finite_acc = torch.ones(1, device=self.device, dtype=torch.int32)
         # Dassl/dassl/optim/optimizer.py:13-142 and lr_scheduler.py:83-155: OPTIM.NAME picks the update rule, OPTIM.LR_SCHEDULER
         # (+ WARMUP_*) the schedule; a config without those keys is sgd / single_step / no warm-up
@@ -322,7 +325,10 @@ class GLP_OT_SVLoRA:
         step (loss.item(), accuracy, sklearn AUC) shrink to one small copy per summary that is actually looked at.
         cfg.TRAIN.METRICS_EVERY = N > 1 skips the summary on the other steps altogether; TRAIN.SYNC_EVERY_STEP raises
         a non-finite loss inside the call as the reference does; TRAIN.HOST_METRICS computes the metrics with the
-        host (numpy) versions."""
+        host (numpy) versions.  TRAINER.LAMBDA_FAIRNESS != 0: the engine's loss already is CE + lambda * F (:946-948), so the
+        device summary reports it as it stands; the host summary stays an independent check - it takes the engine's CE alone
+        (loss_terms[0]) and adds the term it computes itself from the returned probabilities, never the device total plus
+        a second term."""
         image, label, _, attr = self.parse_batch_train(batch)
         # PREC 'amp': the reference's branch calls self.model(image) WITHOUT the attribute (uniform group mix) and has
         # no fairness term (trainers/GLP_OT_SVLoRA.py:890-898; SURVEY §5 quirk 5); autocast itself is not mirrored (fp32)
@@ -343,8 +349,7 @@ class GLP_OT_SVLoRA:
         self._finite_acc.mul_(out["finite"])
         if getattr(train_cfg, "SYNC_EVERY_STEP", False):
             self.check_finite()
-        if want and out["prob"].shape[1] == 2 and (lam == 0.0 or attr is None or amp) \
-                and not getattr(train_cfg, "HOST_METRICS", False):
+        if want and out["prob"].shape[1] == 2 and not getattr(train_cfg, "HOST_METRICS", False):
             # (the counts come with the step when the engine was asked for them - build_model - and are copied out of its
             # static buffer like the loss; otherwise they are formed here, behind the SGD step)
             counts = out["counts"].clone() if "counts" in out else ops.eval_counts(out["prob"], label.contiguous(), None, 0)
@@ -352,8 +357,8 @@ class GLP_OT_SVLoRA:
         elif want:
             self.check_finite()
             logits, prob = out["logits"], out["prob"]
-            loss = float(out["loss"])
-            if lam != 0.0 and attr is not None and not amp:             # detached fairness term (:930-948)
+            loss = float(out["loss_terms"][0] if "loss_terms" in out else out["loss"])
+            if lam != 0.0 and attr is not None and not amp:             # the fairness term on the host (:930-948)
                 correct = prob[torch.arange(len(label)), label]
                 vals = torch.stack([1 - correct[attr == g].mean() for g in torch.unique(attr)])
                 loss += lam * float(torch.mean(torch.abs(vals - vals.mean())))

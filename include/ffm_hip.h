@@ -52,7 +52,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* ---- epilogue flags for ffm_gemm_nt ------------------------------------ */
@@ -503,6 +503,30 @@ int ffm_head_fwd(const void* f, const float* tbar, const float* logit_scale, flo
 int ffm_ce_loss(const float* logits_img, const int64_t* label, float* logits, float* prob,
                 float* loss, float* dlogits_img, int32_t* finite_flag, int nb, int S, int n_cls,
                 void* stream);
+
+/*
+ * ffm_ce_loss plus the group-confidence-gap term of the loss (TRAINER.LAMBDA_FAIRNESS; the reference's 'confidence'
+ * variant, trainers/GLP_OT_SVLoRA.py:908-914, 928-948), optionally with the term's gradient.  One block, all fp32.
+ * With z[b] = mean_s logits_img[b*S+s], p = softmax(z), c_b = p[b][label_b]:
+ *   logits, prob:     what ffm_ce_loss writes, bit for bit
+ *   present groups:   the g in [0, G) with n_g >= 1 samples (torch.unique(attr), :933), P of them.  A sample whose attr lies
+ *                     outside [0, G) takes part in the cross-entropy and not in the term
+ *   m_g = 1 - (1/n_g) sum_{b in g} c_b;  M = (1/P) sum_g m_g;  F = (1/P) sum_g |m_g - M|  (:934-944);  P <= 1: F = 0
+ *   terms[0] = cls = mean_b CE;  terms[1] = F;  loss[0] = cls + lambda * F (:946-948);  *finite_flag follows loss[0]
+ *   gstat (may be NULL): [G][2] = {m_g, n_g}, m_g = 0 for an absent group
+ *   dlogits_img[b*S+s][k] = (1/S) [ (p_bk - d_{k,y_b}) / nb + with_grad * lambda * kappa_{g(b)} * c_b * (d_{k,y_b} - p_bk) ]
+ *     kappa_g = -(sigma_g - sbar) / (P n_g),  sigma_g = sign(m_g - M) (sign(0) = 0),  sbar = (1/P) sum_g sigma_g;
+ *     kappa = 0 for a sample outside the groups
+ * with_grad = 0 is the reference: it builds the term from detached values, so dlogits_img is
+ * ffm_ce_loss's bit for bit.  with_grad = 1 is an extension beyond the reference: the autograd gradient of cls + lambda F
+ * with the term NOT detached.  Every sum is a fixed-order reduction (strided per-thread sums, then the shared-memory
+ * tree; groups in ascending index): two runs give identical bits.  attr: [nb] int32 (per sample, also with S > 1).
+ * FFM_EINVAL: a NULL pointer (gstat and finite_flag excepted), nb / S / n_cls <= 0, n_cls > 8, G <= 0, G > FFM_MAX_GROUPS.
+ */
+int ffm_ce_fair_loss(const float* logits_img, const int64_t* label, const int32_t* attr,
+                     float* logits, float* prob, float* loss, float* terms, float* gstat,
+                     float* dlogits_img, int32_t* finite_flag, int nb, int S, int n_cls, int G,
+                     float lambda, int with_grad, void* stream);
 
 /*
  * Head backward: df [B*L, D] dtype (row l = 0 gets zeros) and
