@@ -190,11 +190,15 @@ template <> struct Act<bf16_t> {
     }
 };
 
+// An attribute value outside [0, G) is "unknown": -1 in every slot a kernel keeps it in, mixed like attr == NULL.
+__device__ __forceinline__ int group_id(int a, int G) { return (unsigned)a < (unsigned)G ? a : -1; }
+
 // pi_b[g]: 0.7 on the sample's own group, 0.3/(G-1) elsewhere; uniform when
-// attr is NULL (trainers/GLP_OT_SVLoRA.py:453-462).
+// attr is NULL (trainers/GLP_OT_SVLoRA.py:453-462) or the sample's value is unknown.
 __device__ __forceinline__ float group_mix_w(const int32_t* attr, int sample, int g, int G, float lambda_group) {
     if (attr == nullptr) return 1.0f / (float)G;
-    int a = attr[sample];
+    const int a = group_id(attr[sample], G);
+    if (a < 0) return 1.0f / (float)G;
     return (a == g) ? lambda_group : (1.0f - lambda_group) / (float)(G - 1);
 }
 

@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(gemm_kargs px) {
     if constexpr (RK) {
         if (has_lora) {
             if (tid < p.G * r) Sg[tid] = sg_v;
-            if (tid < BM) Ga[tid] = ga_v;
+            if (tid < BM) Ga[tid] = group_id(ga_v, p.G);      // outside [0, G): unknown = -1, so the SBt row is in range
         }
     }
     if constexpr (VL) {

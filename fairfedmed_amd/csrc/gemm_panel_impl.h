@@ -499,7 +499,7 @@ __attribute__((amdgpu_waves_per_eu(panel_waves_per_eu<MF, NF, RK, PWV>(), panel_
         for (int it = 0; it < NGI; ++it) {
             asm volatile("" : "+v"(gav[it]));
             const int i = tid + it * PT;
-            if (i < BMp) Ga[i] = gav[it];
+            if (i < BMp) Ga[i] = group_id(gav[it], p.G);      // outside [0, G): unknown = -1, so Sg[a * r + j] is in range
         }
     }
     if constexpr (LNIN) {

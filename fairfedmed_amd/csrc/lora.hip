@@ -255,7 +255,7 @@ __global__ __launch_bounds__(LDM_WAVES * 64) void lora_down_mfma_kernel(
     const int grow = row0 + col;
     const bool rok = grow < M;
     const int sample = (rok ? grow : M - 1) / rows_per_sample;
-    const int ga = attr ? attr[sample] : -1;
+    const int ga = attr ? group_id(attr[sample], G) : -1;      // (outside [0, G): unknown, the uniform mix)
     const float w_own = lambda_group, w_oth = (1.0f - lambda_group) / (float)(G > 1 ? G - 1 : 1), w_uni = 1.0f / (float)G;
     const bool do_ds = t_fwd && ds_part;
     float wv[4];

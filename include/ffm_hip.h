@@ -117,7 +117,9 @@ typedef struct ffm_gemm_args {
      * backward), ts = scaling * t * s_b feeds the rank-r update above, `ts` is ignored. */
     const void*  rk;    /* [16, K] dtype, row stride K: packed lora_A^T or lora_B (rows >= r zero), see ffm_lora_pack_multi */
     const float* S;     /* lora_S [G, r] */
-    const int32_t* attr;/* [nsamples] group index or NULL (uniform mix) */
+    const int32_t* attr;/* [nsamples] group index or NULL (uniform mix); a value outside [0, G) (the loaders' -1, any other
+                         * negative value, an index >= G) is "unknown": that sample takes the uniform 1/G mix, in ts and in
+                         * the dS partials alike, bit-identical to what attr == NULL gives it */
     float*       t_out; /* optional [M, r]: t  */
     float*       ts_out;/* optional [M, r]: ts */
     const float* t_fwd; /* optional [M, r]: with ds_part, dS partials = sum_rows pi_b scaling t_fwd t */
@@ -430,7 +432,9 @@ int ffm_attention_bwd_lnstat(const void* qkv, const void* out, const void* dout,
  *   t[m][j]  = sum_k x[m][k] * P[k][j]        (P = lora_A [K,r], layout_rk = 0)
  *            = sum_k x[m][k] * P[j][k]        (P = lora_B [r,K], layout_rk = 1: u = g B^T)
  *   ts[m][j] = scaling * t[m][j] * s_b[j],  s_b = pi_b . S,  b = m / rows_per_sample
- * attr: int32 [nsamples] group index, or NULL for the uniform 1/G mix (:462).
+ * attr: int32 [nsamples] group index, or NULL for the uniform 1/G mix (:462).  A value outside [0, G) is "unknown" (as
+ * in ffm_ce_fair_loss / ffm_eval_counts): that sample takes the uniform mix too, in ts and in the dS partials, with the
+ * same arithmetic as attr == NULL (the reference raises there, so this is the library's own definition).
  * If t_fwd != NULL also accumulates the dS partials
  *   ds_part[blk][g][j] = sum_{m in blk} pi_{b(m)}[g] * scaling * t_fwd[m][j] * t[m][j]
  * The call writes exactly ffm_lora_down_blocks(M, K, r, dtype) partial rows of G * r floats (the count a reduction over

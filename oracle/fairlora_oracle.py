@@ -45,11 +45,21 @@ Tensor = torch.Tensor
 def group_mix(attr: Optional[Tensor], num_groups: int, lambda_group: float = 0.7,
               dtype=torch.float32) -> Tensor:
     """pi[b, g]: 0.7 on the sample's own group, 0.3/(G-1) on the others;
-    uniform 1/G when attr is None (trainers/GLP_OT_SVLoRA.py:453-462)."""
+    uniform 1/G when attr is None (trainers/GLP_OT_SVLoRA.py:453-462).
+
+    BEYOND THE REFERENCE: a row whose attribute lies outside [0, G) (the loaders' -1 "unknown", any other negative
+    value, an index at or above G) gets the uniform 1/G of `attr is None`.  The reference raises in F.one_hot on such
+    a value, so there is no parity to keep there; this is the rule the HIP kernels hold.  Rows with
+    a valid attribute go through the reference's expression unchanged."""
     if attr is None:
         return torch.full((1, num_groups), 1.0 / num_groups, dtype=dtype)
-    onehot = F.one_hot(attr.long(), num_classes=num_groups).to(dtype)
-    return onehot * lambda_group + (1 - onehot) * (1 - lambda_group) / (num_groups - 1)
+    a = attr.long()
+    known = (a >= 0) & (a < num_groups)
+    onehot = F.one_hot(torch.where(known, a, torch.zeros_like(a)), num_classes=num_groups).to(dtype)
+    pi = onehot * lambda_group + (1 - onehot) * (1 - lambda_group) / (num_groups - 1)
+    if bool(known.all()):
+        return pi
+    return torch.where(known[:, None], pi, torch.full_like(pi, 1.0 / num_groups))
 
 
 def fairlora_linear(x: Tensor, W: Tensor, b: Optional[Tensor], A: Tensor, S: Optional[Tensor], Bm: Tensor,

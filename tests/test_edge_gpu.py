@@ -340,3 +340,202 @@ def test_fp16_trainer_keeps_training_through_an_injected_overflow():
     torch.cuda.synchronize()
     assert tr.engine.overflow_steps() >= 1 and bool(torch.isfinite(tr.engine.params.flat).all())
     assert tr.engine.grad_scale < 2.0 ** 30
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Attribute values outside [0, G): "unknown" -> the uniform 1/G mix of attr=None, in every engine (the
+# kernels one by one: tests/test_group_mix_gpu.py; the oracle's rule: tests/test_group_mix_cpu.py).  set_fairness stays 0:
+# how the loss term treats unknown samples is pinned by tests/test_fairness_loss_*.
+# ---------------------------------------------------------------------------------------------------------------------
+def unknown_pattern(G, n):
+    """The fixed pattern of tests/test_group_mix_gpu.py: valid groups and the unknown values {-2, -1, G, G + 1}."""
+    return torch.tensor(([0, -1, G - 1, G, 1, -2, 0, G + 1, 1] * (n // 9 + 1))[:n], dtype=torch.int64)
+
+
+def with_attr(batch, attr):
+    out = dict(batch)
+    out["attrs"] = attr[:, None].clone()
+    return out
+
+
+@pytest.mark.parametrize("rank,G", [(12, 3), (16, 3), (24, 3), (32, 8)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_step_vs_oracle_with_unknown_attributes(rank, G, dtype):
+    """test_step_vs_oracle_over_ranks_and_groups (its bounds) on nine samples carrying the mixed pattern: the fp32 engine
+    (VALU down projections) and the 16-bit engines (fused rank stages) against the one extended oracle."""
+    from oracle import fairlora_oracle as O
+    from fairfedmed_amd.engine import FairLoRAEngine
+    bs = 9
+    mcfg = C.vit_tiny(rank=rank, num_groups=G)
+    sd = synth.make_state_dict(mcfg, seed=rank, lora_init="random")
+    batch = with_attr(synth.make_batch(mcfg, bs, seed=77 + rank), unknown_pattern(G, bs))
+    keys = synth.trainable_keys(mcfg)
+    eng = FairLoRAEngine(mcfg, sd, dtype=dtype, max_images=bs)
+    out = eng.forward_backward(batch["img"].cuda(), batch["attrs"].t()[0].cuda(), batch["label"].cuda())
+    loss, logits, grads = O.loss_and_grads(sd, batch, mcfg, keys)
+    f32 = dtype == torch.float32
+    assert int(out["finite"]) == 1
+    assert rel(out["logits"], logits) < (2e-5 if f32 else 3e-2)
+    assert abs(float(out["loss"]) - float(loss)) <= (2e-5 if f32 else 1e-2) * abs(float(loss))
+    for k in keys:
+        g, ref = eng.params.view(k, "grad"), grads[k]
+        if float(ref.abs().max()) == 0.0:
+            assert float(g.abs().max()) < 1e-12, k
+        elif f32:
+            assert rel(g, ref) < 2e-3, (k, rel(g, ref))
+        else:
+            assert cos(g, ref) > 0.985, (k, cos(g, ref))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_oct3d_step_with_unknown_attributes(dtype):
+    """The 3D OCT configuration (rows_per_sample = L * S: a sample's mix covers all its slice groups), bounds of
+    tests/test_engine_gpu.py::test_tiny_step_vs_oracle_and_golden against the oracle."""
+    from oracle import fairlora_oracle as O
+    from fairfedmed_amd.engine import FairLoRAEngine
+    bs = 6
+    mcfg = C.vit_tiny_3d(rank=4, dim_per_3d_slice=4)
+    sd = synth.make_state_dict(mcfg, seed=1, lora_init="random")
+    batch = with_attr(synth.make_batch(mcfg, bs, seed=1234), unknown_pattern(3, bs))
+    keys = synth.trainable_keys(mcfg)
+    eng = FairLoRAEngine(mcfg, sd, dtype=dtype, max_images=2 * bs)
+    out = eng.forward_backward(batch["img"].cuda(), batch["attrs"].t()[0].cuda(), batch["label"].cuda())
+    torch.cuda.synchronize()
+    f32 = dtype == torch.float32
+    assert int(out["finite"]) == 1
+    loss, logits, grads = O.loss_and_grads(sd, batch, mcfg, keys)
+    assert rel(out["logits"], logits) < (1e-5 if f32 else 2e-2)
+    for k in keys:
+        g, ref = eng.params.view(k, "grad"), grads[k]
+        if float(ref.abs().max()) == 0.0:
+            assert float(g.abs().max()) < 1e-12, k
+        elif f32:
+            assert rel(g, ref) < 2e-3, (k, rel(g, ref))
+        else:
+            assert cos(g, ref) > 0.99 and rel(g, ref) < 0.15, (k, cos(g, ref), rel(g, ref))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_rn_step_with_unknown_attributes(dtype):
+    """The tiny RN50 engine (rows_per_sample runs 49 ... 3136 through its stages), bounds of
+    tests/test_engine_rn_gpu.py::test_rn_step_vs_oracle_and_golden against the oracle."""
+    import copy
+    from oracle import fairlora_oracle as O
+    from fairfedmed_amd.engine_rn import create_engine
+    bs, G = 6, 2
+    mcfg = C.rn_tiny(rank=4, num_groups=G)
+    sd = synth.make_state_dict(mcfg, seed=1, lora_init="random")
+    batch = with_attr(synth.make_batch(mcfg, bs, seed=1234), unknown_pattern(G, bs))
+    keys = synth.trainable_keys(mcfg)
+    eng = create_engine(mcfg, sd, dtype=dtype, max_images=bs)
+    out = eng.forward_backward(batch["img"].cuda(), batch["attrs"].t()[0].cuda(), batch["label"].cuda())
+    torch.cuda.synchronize()
+    f32 = dtype == torch.float32
+    assert int(out["finite"]) == 1
+    loss, logits, grads = O.loss_and_grads(copy.deepcopy(sd), batch, mcfg, keys)
+    assert rel(out["logits"], logits) < (3e-5 if f32 else 0.15)
+    small = []
+    for k in keys:
+        g, ref = eng.params.view(k, "grad"), grads[k]
+        if float(ref.abs().max()) == 0.0:
+            assert float(g.abs().max()) < 1e-12, k
+        elif f32:
+            assert rel(g, ref) < 1e-2 and cos(g, ref) > 1 - 1e-5, (k, rel(g, ref))
+        elif g.numel() >= 64:
+            assert cos(g, ref) > 0.6, (k, cos(g, ref))
+        else:
+            small.append(k)
+    if small:                                                        # (the 8-element dS tensors are judged together there too)
+        cat = lambda f: torch.cat([torch.as_tensor(f(k)).double().cpu().flatten() for k in small])
+        assert cos(cat(lambda k: eng.params.view(k, "grad")), cat(lambda k: grads[k])) > 0.6
+
+
+def test_vitb16_bs32_panel_path_with_a_quarter_of_the_batch_unknown():
+    """tests/test_engine_gpu.py::test_vitb16_bs32_panel_path_vs_fp32_engine, its arrangement and bounds, with every fourth
+    sample's attribute unknown (-1, G, -2, G + 1 in turn): the bf16 engine's panel rank stages against the fp32 engine's
+    VALU down projections."""
+    from fairfedmed_amd import ops
+    from fairfedmed_amd.engine import FairLoRAEngine
+    mcfg = C.vit_b16(rank=8)
+    G = mcfg.lora.num_groups
+    sd = synth.make_state_dict(mcfg, seed=1, lora_init="random")
+    batch = synth.make_batch(mcfg, 32, seed=77, signal=0.2)
+    attr = batch["attrs"].t()[0].clone()
+    attr[0::4] = torch.tensor([-1, G, -2, G + 1] * 2)
+    img, attr, label = batch["img"].cuda(), attr.cuda(), batch["label"].cuda()
+    w = mcfg.vision.width
+    assert ops.gemm_tiles_m(32 * 197, 4 * w, w, 2 | 4 | 32 | 64, 8, torch.bfloat16, True) != \
+        ops.gemm_tiles_m(32 * 197, 4 * w, w, 2 | 4 | 32 | 64, 8, torch.bfloat16, False), "panel kernel not selected"
+    ref = FairLoRAEngine(mcfg, sd, dtype=torch.float32, max_images=32)
+    eng = FairLoRAEngine(mcfg, sd, dtype=torch.bfloat16, max_images=32)
+    assert eng.vis.blocks[0].packed is not None and ref.vis.blocks[0].packed is None
+    losses = []
+    for step in range(3):
+        o_ref = ref.forward_backward(img, attr, label)
+        o = eng.forward_backward(img, attr, label)
+        torch.cuda.synchronize()
+        assert int(o["finite"]) == 1
+        losses.append((float(o["loss"]), float(o_ref["loss"])))
+        assert abs(losses[-1][0] - losses[-1][1]) <= 1e-2 * abs(losses[-1][1]), losses
+        if step == 0:
+            assert rel(o["logits"], o_ref["logits"]) < 5e-2
+            for k in synth.trainable_keys(mcfg):
+                g, gr = eng.params.view(k, "grad"), ref.params.view(k, "grad")
+                assert cos(g, gr) > 0.985, (k, cos(g, gr))
+                assert abs(float(g.norm()) - float(gr.norm())) <= 4e-2 * float(gr.norm()) + 1e-12, k
+        ref.sgd_step(1e-3, 0.9, 5e-4)
+        eng.sgd_step(1e-3, 0.9, 5e-4)
+
+
+@pytest.mark.parametrize("rank", [4, 24], ids=["fused-rank-stage", "stand-alone-down-projection"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_all_unknown_attributes_equal_no_attribute_bit_for_bit(rank, dtype):
+    """forward, infer and forward_backward with an all -1 attribute vector against attr=None: the same launches with the
+    same arithmetic, so logits and every gradient are torch.equal."""
+    from fairfedmed_amd.engine import FairLoRAEngine
+    bs = 9
+    mcfg = C.vit_tiny(rank=rank, num_groups=3)
+    sd = synth.make_state_dict(mcfg, seed=3, lora_init="random")
+    batch = synth.make_batch(mcfg, bs, seed=31)
+    img, label = batch["img"].cuda(), batch["label"].cuda()
+    unknown = torch.full((bs,), -1, dtype=torch.int64, device="cuda")
+    eng = FairLoRAEngine(mcfg, sd, dtype=dtype, max_images=bs)
+    keys = synth.trainable_keys(mcfg)
+    got = {}
+    for name, attr in (("none", None), ("unknown", unknown)):
+        fwd = eng.forward(img, attr).clone()
+        inf = eng.infer(img, attr).clone()
+        out = eng.forward_backward(img, attr, label)
+        torch.cuda.synchronize()
+        got[name] = (fwd, inf, out["logits"].clone(), out["loss"].clone(), {k: eng.params.view(k, "grad").clone() for k in keys})
+    a, b = got["none"], got["unknown"]
+    assert bool(torch.isfinite(a[2]).all())
+    for i, what in enumerate(("forward", "infer", "forward_backward logits", "loss")):
+        assert torch.equal(a[i], b[i]), what
+    for k in keys:
+        assert torch.equal(a[4][k], b[4][k]), k
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_captured_step_replays_unknown_attributes_like_the_eager_step(dtype):
+    """The graph is captured on a valid attribute vector (the static buffer's zeros); a replay after the mixed pattern is
+    copied into that buffer trains bit-identically to the eager step of a twin engine (tests/test_graph_step_gpu.py)."""
+    from fairfedmed_amd.engine import FairLoRAEngine
+    from tests.test_graph_step_gpu import LR, MU, WD, same, state_of
+    bs = 9
+    mcfg = C.vit_tiny(rank=4, num_groups=3)
+    sd = synth.make_state_dict(mcfg, seed=1, lora_init="random")
+    eager, graphed = (FairLoRAEngine(mcfg, sd, dtype=dtype, max_images=bs) for _ in range(2))
+    step = graphed.capture_train_step(bs, LR, MU, WD, repeats=2)
+    for i, attr in enumerate((unknown_pattern(3, bs), torch.arange(bs) % 3, unknown_pattern(3, bs).flip(0))):
+        batch = synth.make_batch(mcfg, bs, seed=40 + i, signal=0.2)
+        img, attr, label = batch["img"].cuda(), attr.cuda(), batch["label"].cuda()
+        loss_e = eager.forward_backward(img, attr, label)["loss"].clone()
+        eager.sgd_step(LR, MU, WD, repeats=2)
+        loss_g = step.run(img, attr, label)["loss"].clone()
+        torch.cuda.synchronize()
+        assert same(loss_g, loss_e), (i, float(loss_g), float(loss_e))
+        a, b = state_of(graphed), state_of(eager)
+        for k in ("flat", "momentum", "grad", "steps"):
+            assert same(a[k], b[k]), f"step {i}: {k} of the graphed engine differs from the eager one"
+        assert bool(torch.isfinite(a["flat"]).all())

@@ -153,8 +153,17 @@ def test_gemm_panel_plain(ops, M, N, K, mode, h16):
 @H16
 def test_gemm_panel_fairlora(ops, case, M, r, G, use_attr, h16):
     """The four FairLoRA GEMMs of a block on the panel kernel: t / ts / dS partials / fused rank-r update / GELU."""
-    dt = h16
-    width, rps = 768, 197
+    rps = 197
+    nsamp = (M + rps - 1) // rps
+    attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
+    panel_fairlora_case(ops, case, M, r, G, attr, rps, h16)
+
+
+def panel_fairlora_case(ops, case, M, r, G, attr, rps, dt, before_checks=None):
+    """Body of test_gemm_panel_fairlora for a given attribute vector ([ceil(M / rps)] int32 or None) and rows per sample.
+    `before_checks(res)` (tests/test_group_mix_gpu.py) sees every tensor of the launch and its float64 reference before
+    this function's own assertions run."""
+    width = 768
     deriv = case == "proj_dx_deriv"               # dX(c_proj) with the saved tensor = quick_gelu'(pre) (gelu_deriv)
     case = "proj_dx" if deriv else case
     N, K = (4 * width, width) if case in ("fc_fwd", "proj_dx") else (width, 4 * width)
@@ -166,11 +175,9 @@ def test_gemm_panel_fairlora(ops, case, M, r, G, use_attr, h16):
     P = rnd(K, r, scale=0.1, seed=73)
     S = rnd(G, r, seed=74)
     lw = rnd(N, r, seed=75) if kr else rnd(r, N, seed=75)
-    nsamp = (M + rps - 1) // rps
-    attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
     rk = torch.zeros(16, K, device="cuda", dtype=dt)
     ops.PackPlan([(P, False, rk)], dt, "cuda").run()
-    out = torch.empty(M, N, device="cuda", dtype=dt)
+    out = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
     t, ts = torch.full((M, r), float("nan"), device="cuda"), torch.full((M, r), float("nan"), device="cuda")
     kw, bwd = {}, kr
     t_fwd = rnd(M, r, seed=76) if bwd else None
@@ -201,6 +208,11 @@ def test_gemm_panel_fairlora(ops, case, M, r, G, use_attr, h16):
         if deriv:
             kw["gelu_deriv"] = True
     ops.gemm_nt(a, b, out, lw=lw, lw_is_kr=kr, rankop=ro, b_packed=ops.pack_b(b), **kw)
+    from types import SimpleNamespace
+    res = SimpleNamespace(t=t, ts=ts, out=out, act=act, dsp=dsp, ref_t=ref_t, ref_ts=ref_ts, ref_out=ref, pi_rows=pi_rows,
+                          t_fwd=t_fwd, attr=attr, rps=rps, scaling=0.25, dt=dt)
+    if before_checks is not None:
+        before_checks(res)
     check(t, ref_t, 2e-5, "t")
     check(ts, ref_ts, 2e-5, "ts")
     check(out, ref, tol(dt), "fused out")
@@ -209,6 +221,7 @@ def test_gemm_panel_fairlora(ops, case, M, r, G, use_attr, h16):
         check(act, pre * torch.sigmoid(1.702 * pre), tol(dt), "quick_gelu(pre)")
     if bwd:
         check(dsp.double().sum(0), pi_rows.t() @ (0.25 * t_fwd.double() * ref_t), 5e-5, "dS")
+    return res
 
 
 @pytest.mark.mask_tolerant
@@ -219,8 +232,16 @@ def test_gemm_panel_lgrad_partials(ops, M, r, G, use_attr, h16):
     gradient reductions of the block - dB(c_fc) = dpre^T ts1 from the rows it stores and dA(c_proj) = act^T us from
     quick_gelu(pre) and its own ts.  Held to float64 on the 16-bit tensors the kernel itself produced, and to the
     reduction kernel it replaces (ffm_lora_grad_partial); everything else the launch writes must not move."""
-    dt = h16
-    width, rps = 768, 197
+    rps = 197
+    nsamp = (M + rps - 1) // rps
+    attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
+    panel_lgrad_case(ops, M, r, G, attr, rps, h16)
+
+
+def panel_lgrad_case(ops, M, r, G, attr, rps, dt, before_checks=None):
+    """Body of test_gemm_panel_lgrad_partials for a given attribute vector and rows per sample (`before_checks`: as in
+    panel_fairlora_case, on the launch WITH the partial products)."""
+    width = 768
     N, K = 4 * width, width
     nlg = ops.gemm_lgrad_rows(M, N, K, r, dt, True)
     if nlg <= 0:
@@ -229,8 +250,6 @@ def test_gemm_panel_lgrad_partials(ops, M, r, G, use_attr, h16):
     nrows = ops.gemm_tiles_m(M, N, K, flags, r, dt, True)
     a, b = rnd(M, K, dt=dt, seed=70), rnd(N, K, dt=dt, scale=K ** -0.5, seed=71)
     P, S, lw = rnd(K, r, scale=0.1, seed=73), rnd(G, r, seed=74), rnd(N, r, seed=75)
-    nsamp = (M + rps - 1) // rps
-    attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
     rk = torch.zeros(16, K, device="cuda", dtype=dt)
     ops.PackPlan([(P, False, rk)], dt, "cuda").run()
     pre = rnd(M, N, dt=dt, seed=78)
@@ -250,6 +269,14 @@ def test_gemm_panel_lgrad_partials(ops, M, r, G, use_attr, h16):
     pa = torch.full((nlg, N, r), float("nan"), device="cuda")
     out, t, ts, dsp = run((ts1, pc, pa))
     out0, t0, ts0, dsp0 = run(None)
+    if before_checks is not None:
+        from types import SimpleNamespace
+        ref_t = a.double() @ P.to(dt).double()
+        rows = torch.arange(M, device="cuda") // rps
+        pi = mix(attr, G)
+        pi_rows = pi[rows] if attr is not None else pi.expand(M, G)
+        before_checks(SimpleNamespace(t=t, ts=ts, out=None, act=None, dsp=dsp, ref_t=ref_t, ref_ts=0.25 * ref_t * (pi_rows @ S.double()),
+                                      ref_out=None, pi_rows=pi_rows, t_fwd=t_fwd, attr=attr, rps=rps, scaling=0.25, dt=dt))
     assert torch.equal(out, out0) and torch.equal(t, t0) and torch.equal(ts, ts0) and torch.equal(dsp, dsp0)
     assert not torch.isnan(pc).any() and not torch.isnan(pa).any()
     x = pre.float()
@@ -487,10 +514,14 @@ def test_attention_fwd_bwd(ops, dt, B, L, heads, causal):
 
 # ------------------------------------------------------------------ LoRA ---
 def mix(attr, G, lam=0.7):
+    """pi_b in float64; a value outside [0, G) is "unknown" and takes the uniform row of attr=None."""
     if attr is None:
         return torch.full((1, G), 1.0 / G, device="cuda", dtype=torch.float64)
-    oh = torch.nn.functional.one_hot(attr.long(), G).double()
-    return oh * lam + (1 - oh) * (1 - lam) / (G - 1)
+    a = attr.long()
+    known = (a >= 0) & (a < G)
+    oh = torch.nn.functional.one_hot(torch.where(known, a, torch.zeros_like(a)), G).double()
+    pi = oh * lam + (1 - oh) * (1 - lam) / (G - 1)
+    return torch.where(known[:, None], pi, torch.full_like(pi, 1.0 / G))
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
@@ -820,8 +851,17 @@ def test_gemm_panel_layernorm_backward_fold(ops, M, r, G, use_attr, h16):
     d = W beta + b as rows 14 / 15 (rank <= 14: its t[14] / t[15] are the two sums against them), fed those partial rows, stores
     rstd (gamma g_h - c1/K - xhat c2/K) + res: held to float64 autograd THROUGH LayerNorm -> FairLoRA linear on the same
     operands (the algebra of include/ffm_hip.h), and to the unfolded pair (plain dX product, then ffm_layernorm_bwd)."""
-    dt = h16
-    width, rps = 768, 197
+    rps = 197
+    nsamp = (M + rps - 1) // rps
+    attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
+    panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, h16)
+
+
+def panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, dt, before_checks=None):
+    """Body of test_gemm_panel_layernorm_backward_fold for a given attribute vector and rows per sample.  `before_checks`
+    (as in panel_fairlora_case) is called twice: for the LNB_STAT launch (rank operand P2 / S2) and for the LNB_APPLY
+    launch (rank operand B_fc / S, whose ts is `us`; that launch stores no t)."""
+    width = 768
     N, K = 4 * width, width                                            # c_fc: x [M, 768] -> pre [M, 3072]
     flags1 = 2 | 4 | 32 | 64 | 512 | 2048
     tn = ops.gemm_tiles_n(M, N, K, flags1, r, dt, True)
@@ -837,8 +877,6 @@ def test_gemm_panel_layernorm_backward_fold(ops, M, r, G, use_attr, h16):
     Wfc = g(N, K, dt=dt, scale=K ** -0.5, seed=304)                     # frozen c_fc weight [3072, 768]
     bfc = 0.1 * g(N, seed=305)
     A, Bm, S = g(K, r, scale=0.1, seed=306), g(r, N, scale=0.1, seed=307), g(G, r, seed=308)
-    nsamp = (M + rps - 1) // rps
-    attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
     pi = mix(attr, G)
     rows = torch.arange(M, device="cuda") // rps
     sb = (pi[rows] if attr is not None else pi.expand(M, G)) @ S.double()                  # [M, r]
@@ -877,6 +915,13 @@ def test_gemm_panel_layernorm_backward_fold(ops, M, r, G, use_attr, h16):
     for a_, b_ in zip(got, base):
         assert torch.equal(a_, b_), "FFM_EPI_LNB_STAT must not move anything else the launch writes"
     dpre = got[0]
+    pi_rows = pi[rows] if attr is not None else pi.expand(M, G)
+    if before_checks is not None:
+        from types import SimpleNamespace
+        ref_t2 = gi.double() @ P2.to(dt).double()
+        before_checks(SimpleNamespace(t=got[1], ts=got[2], out=None, act=None, dsp=got[3], ref_t=ref_t2,
+                                      ref_ts=sigma * ref_t2 * (pi_rows @ S2.double()), ref_out=None, pi_rows=pi_rows, t_fwd=t_fwd,
+                                      attr=attr, rps=rps, scaling=sigma, dt=dt))
     assert not torch.isnan(part).any()
     P = part.double().sum(0)
     assert float(P[:, 0].abs().max()) == 0.0                            # (slot 0: reserved)
@@ -906,7 +951,18 @@ def test_gemm_panel_layernorm_backward_fold(ops, M, r, G, use_attr, h16):
 
     g1, us, dsp = run2(ops.LnBwdApply(part, tn, x, gamma, mean32, rstd32, ag, gres))
     gh, us0, dsp0 = run2(None)
-    assert torch.equal(us, us0) and torch.equal(dsp, dsp0)
+    if before_checks is not None:
+        ref_u = dpre.double() @ Bm.t().to(dt).double()                    # u = dpre B_fc^T on the operand as the kernel holds it
+        before_checks(SimpleNamespace(t=None, ts=us, out=None, act=None, dsp=dsp, ref_t=ref_u, ref_ts=sigma * ref_u * sb,
+                                      ref_out=None, pi_rows=pi_rows, t_fwd=t_fwd1, attr=attr, rps=rps, scaling=sigma, dt=dt))
+    if ops.gemm_tile_shape(M, K, N, 2 | 4 | 64 | 4096, r, dt, True)[0] == ops.gemm_tile_shape(M, K, N, 2 | 4 | 64, r, dt, True)[0]:
+        assert torch.equal(us, us0) and torch.equal(dsp, dsp0)
+    else:
+        # FFM_PANEL_MASK with the K split: FFM_EPI_LNB_APPLY exists on the 4-wave 160 x 128 tile only, the plain dX product takes
+        # the 8-wave K-split tile - two kernels that add the K slices in different orders, so equal to fp32 rounding
+        # (the bounds every t / ts / dS check of this file uses), not to the bit
+        check(us, us0.double(), 2e-5, "us against the plain launch on the K-split tile")
+        check(dsp.double().sum(0), dsp0.double().sum(0), 5e-5, "dS against the plain launch on the K-split tile")
     assert not torch.isnan(g1.float()).any()
     # float64 autograd through LayerNorm -> FairLoRA linear with the dpre the first launch stored
     (pre64 * dpre.double()).sum().backward()
@@ -1211,7 +1267,8 @@ def test_panel_tile_configurations_behind_the_mask(mask, what):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FFM_PANEL_MASK=str(mask))
     # no -x in the child: the tail then names every failure, not just the first
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-rfE", os.path.join(root, "tests", "test_kernels_gpu.py"), "-m",
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-rfE", os.path.join(root, "tests", "test_kernels_gpu.py"),
+                        os.path.join(root, "tests", "test_group_mix_gpu.py"), "-m",
                         "mask_tolerant"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "deselected" in r.stdout
