@@ -416,6 +416,65 @@ def test_oct3d_step_with_unknown_attributes(dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_oct3d_step_on_a_uint8_volume_with_tied_extrema(dtype):
+    """What a real OCT volume does to the slice front end and synth.make_batch's random floats never do: a uint8 batch
+    (the engine's uint8 transport) with a black border on every slice and one wholly black slice group.  Where the whole
+    5 x 5 x D field is black the convolution IS the bias; with channel 0 all negative under the highest bias and channel 1 all
+    positive over the lowest, the maximum and the minimum of every ViT image are attained there, thousands of times, and the
+    gradients of proj_per_3d_slice go through the tie counts (the kernels alone: tests/test_slice3d_ties_gpu.py).  Bounds of
+    test_oct3d_step_with_unknown_attributes."""
+    from oracle import fairlora_oracle as O
+    from fairfedmed_amd.engine import FairLoRAEngine
+    bs, border = 4, 8
+    mcfg = C.vit_tiny_3d(rank=4, dim_per_3d_slice=4)
+    D = mcfg.dim_per_3d_slice
+    sd = synth.make_state_dict(mcfg, seed=1, lora_init="random")
+    wk, bk = "proj_per_3d_slice.weight", "proj_per_3d_slice.bias"
+    w = sd[wk] * 2.0 ** -6
+    sd[wk] = torch.stack([-w[0].abs(), w[1].abs(), w[2]]).contiguous()
+    sd[bk] = torch.tensor([1.0, -1.0, 0.0])
+    batch = synth.make_batch(mcfg, bs, seed=1234)
+    u8 = batch["img"].round().clamp(0, 255).to(torch.uint8)
+    u8[:, :, :border] = 0
+    u8[:, :, -border:] = 0
+    u8[:, :, :, :border] = 0
+    u8[:, :, :, -border:] = 0
+    u8[1, D:2 * D] = 0                                                # a blank padding group: one ViT image all black
+    batch["img"] = u8.float()
+    keys = synth.trainable_keys(mcfg)
+    assert wk in keys and bk in keys
+    # the oracle's own convolution: both extrema of every ViT image are tied, or this test proves nothing
+    H = u8.shape[-1]
+    c = torch.nn.functional.conv2d((batch["img"] / 255.0).reshape(-1, D, H, H), sd[wk], sd[bk], padding=2)
+    mn, mx = c.amin(dim=(1, 2, 3), keepdim=True), c.amax(dim=(1, 2, 3), keepdim=True)
+    ties = torch.stack([(c == mn).sum((1, 2, 3)), (c == mx).sum((1, 2, 3))], 1)
+    assert int(ties.min()) > 1000 and ties[3].tolist() == [H * H, H * H], ties.tolist()
+
+    eng = FairLoRAEngine(mcfg, sd, dtype=dtype, max_images=2 * bs)
+    attr, label = batch["attrs"].t()[0].cuda(), batch["label"].cuda()
+    out = eng.forward_backward(u8.cuda(), attr, label)
+    torch.cuda.synchronize()
+    first = eng.params.view(bk, "grad").clone()
+    assert eng.mm_cnt[:2 * bs].cpu().tolist() == ties.tolist()
+    f32 = dtype == torch.float32
+    assert int(out["finite"]) == 1
+    loss, logits, grads = O.loss_and_grads(sd, batch, mcfg, keys)
+    assert rel(out["logits"], logits) < (1e-5 if f32 else 2e-2)
+    for k in keys:
+        g, ref = eng.params.view(k, "grad"), grads[k]
+        if float(ref.abs().max()) == 0.0:
+            assert float(g.abs().max()) < 1e-12, k
+        elif f32:
+            assert rel(g, ref) < 2e-3, (k, rel(g, ref))
+        else:
+            assert cos(g, ref) > 0.99 and rel(g, ref) < 0.15, (k, cos(g, ref), rel(g, ref))
+    # a second step on the same buffers: the tie counters start from zero again
+    eng.forward_backward(u8.cuda(), attr, label)
+    torch.cuda.synchronize()
+    assert torch.equal(eng.params.view(bk, "grad"), first)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 def test_rn_step_with_unknown_attributes(dtype):
     """The tiny RN50 engine (rows_per_sample runs 49 ... 3136 through its stages), bounds of
     tests/test_engine_rn_gpu.py::test_rn_step_vs_oracle_and_golden against the oracle."""

@@ -443,7 +443,9 @@ def test_slice3d_front_end(ops, dt, N, D, H, ps, width):
     check(mnmx[:, 0], mn.flatten().detach(), 2e-6, "min")
     check(mnmx[:, 1], mx.flatten().detach(), 2e-6, "max")
     check(cols, ref_cols.detach(), 2e-5 if dt == torch.float32 else 8e-3, "patchify_minmax")
-    assert cnt.tolist() == [[1, 1]] * N                      # random floats: the extrema are unique
+    # random floats: one pixel attains each extremum.  Tied extrema (black borders, blank slices, saturated regions: counts
+    # in the thousands, gradients divided by them) and H != W are tests/test_slice3d_ties_gpu.py
+    assert cnt.tolist() == [[1, 1]] * N
 
     dcols = rnd(N * P, 3 * ps * ps, dt=dt, seed=34)
     ref_cols.backward(dcols.double())
