@@ -164,6 +164,90 @@ def _ds_rows(rows: int, N: int, K: int, rank: int, dtype, packed: Optional[bool]
     return ops.gemm_tiles_m(rows, N, K, fl, rank, dtype, packed)
 
 
+@dataclass(frozen=True)
+class Switches:
+    """Every Python-side A/B switch of the engines, read from the environment ONCE, when an engine is constructed
+    (FairLoRAEngine.sw).  The kernel-side switches (getenv in csrc/) are the library's own."""
+    red_at: Optional[int] = None           # FFM_RED_AT=0|1|2: where a block's LoRA-gradient reductions start (unset: by row count)
+    lgrad: bool = True                     # FFM_LGRAD=0: the two large reductions as launches again, not inside dX(c_proj)
+    pack_out: bool = True                  # FFM_PACK_OUT=0: patch embedding / final projection weights not in fragment order
+    lnb_fold: bool = True                  # FFM_LNB_FOLD=0: both LayerNorm backward passes as kernels of their own
+    lnb_fold1: bool = True                 # FFM_LNB_FOLD1=0: ln_1's backward pass as its own kernel
+    bn_bwd_fused: bool = True              # FFM_BN_BWD_FUSED=0 (RN50): BatchNorm backward sums from BatchNorm's own pass
+    f16_grad_scale: float = 4096.0         # FFM_F16_GRAD_SCALE: initial (and largest) fp16 gradient scale
+    f16_growth_interval: float = 2000.0    # FFM_F16_GROWTH_INTERVAL: good steps before the scale doubles again
+
+    @classmethod
+    def from_env(cls, env=None) -> "Switches":
+        env = os.environ if env is None else env
+        on = lambda name: env.get(name, "1") != "0"
+        return cls(red_at=int(env["FFM_RED_AT"]) if "FFM_RED_AT" in env else None, lgrad=on("FFM_LGRAD"),
+                   pack_out=on("FFM_PACK_OUT"), lnb_fold=on("FFM_LNB_FOLD"), lnb_fold1=on("FFM_LNB_FOLD1"),
+                   bn_bwd_fused=on("FFM_BN_BWD_FUSED"), f16_grad_scale=float(env.get("FFM_F16_GRAD_SCALE", "4096")),
+                   f16_growth_interval=float(env.get("FFM_F16_GROWTH_INTERVAL", "2000")))
+
+
+@dataclass(frozen=True)
+class Route:
+    """Which fused kernels serve a transformer tower at one row count (tower_route).  0: not folded / a kernel of its own."""
+    ln1: int = 0          # ln_1 inside the qkv product: partial row sums per row the c_proj forward leaves (its column tiles)
+    ln2: int = 0          # ln_2 inside c_fc: partial row sums per row from the out-proj forward
+    lgrad: int = 0        # dB(c_fc) and dA(c_proj) inside dX(c_proj) (FFM_EPI_LGRAD): row tiles of their partials
+    ln2_bwd: int = 0      # ln_2's backward inside dX(c_proj) / dX(c_fc) (FFM_EPI_LNB_*): column tiles of dX(c_proj)
+    ln1_bwd: int = 0      # ln_1's backward inside the attention backward and dX(qkv): partial rows (2 per head)
+    red_at: int = 0       # where the side stream starts a block's LoRA-gradient reductions (_stack_backward)
+
+
+def _can_fold(rank: int, dtype) -> bool:
+    """A tower can take a fold at all (it owns the partial-sum buffers rowp / rowp2 / lnb_part): adapters, 16-bit storage."""
+    return bool(rank) and _is16(dtype)
+
+
+def tower_route(width: int, heads: int, tokens: int, causal: bool, rank: int, dtype, packed: bool, rows: int,
+                sw: Switches) -> Route:
+    """The route of a tower of this geometry at `rows` rows: a pure function of its arguments and of the library's host-side
+    queries (which kernel ffm_gemm_nt picks for a shape, and how it tiles it) - no GPU, no engine.  Every fold needs the
+    panel kernel with the folding epilogue for EACH product it touches at this row count, the rank inside one MFMA tile
+    (0 < rank <= 16: FFM_EPI_RANKOP) and 16-bit storage; tests/test_route_cpu.py pins the regimes of ViT-B/16."""
+    w, r = width, rank
+    # red_at by row count - measured (one call, alternating): configs[1] (6304 rows) 4.65-4.71 / 4.66-4.67 / 4.75-4.76 ms per
+    # step for 0 / 1 / 2; configs[3] (19 700 rows, rank 16: 52 MB of partials per block, whose sum took the attention
+    # backward beside it from 49 to 74 us) 12.45 / 12.42-12.46 / 12.37-12.38
+    red_at = 0 if not r else ((2 if rows > 12608 else 0) if sw.red_at is None else sw.red_at)
+    if not (_can_fold(r, dtype) and r <= 16):
+        return Route(red_at=red_at)
+    tiles = lambda n, k, flags, rk=0: ops.gemm_tiles_n(rows, n, k, flags, rk, dtype, True)
+    # ln_1: the c_proj forward leaves the row sums, the qkv product normalises in its epilogue
+    npj = tiles(w, 4 * w, L.EPI_BIAS | L.EPI_LORA | L.EPI_RESIDUAL | L.EPI_RANKOP | L.EPI_ROWSTATS, r)
+    nq = tiles(3 * w, w, L.EPI_BIAS | L.EPI_LNIN)
+    ln1 = npj if (npj > 0 and npj <= 8 and nq > 0) else 0
+    # ln_2: row sums from the out-proj forward, the FairLoRA c_fc product with the folding epilogue (its rank operand
+    # gamma-scaled), and dA(c_fc) from the raw rows (ffm_lora_grad_partial_ln)
+    npo = tiles(w, w, L.EPI_BIAS | L.EPI_RESIDUAL | L.EPI_ROWSTATS)
+    nf = tiles(4 * w, w, L.EPI_BIAS | L.EPI_LORA | L.EPI_GELU | L.EPI_RANKOP | L.EPI_LNIN, r)
+    ln2 = npo if (npo > 0 and npo <= 8 and nf > 0 and w % 128 == 0 and r <= 16) else 0
+    # FFM_EPI_LGRAD: 0 when the kernel that serves dX(c_proj) has no such epilogue (then the two reduction launches run)
+    lgrad = 0
+    if sw.lgrad and packed and r % 4 == 0:
+        lgrad = max(0, ops.gemm_lgrad_rows(rows, 4 * w, w, r, dtype, True))
+        if lgrad > ops.lora_grad_splits(rows):                # (the partial buffers are sized for the reduction kernel's splits)
+            lgrad = 0
+    # ln_2's backward: needs the forward fold (its W gamma / W beta + b / A^T gamma / A^T beta vectors, rows 14 / 15 of the
+    # rank operand), the LGRAD epilogue beside which dX(c_proj) leaves the two row sums, and both kernels
+    ln2_bwd = 0
+    if sw.lnb_fold and ln2 and lgrad > 0 and r <= 14:
+        f1 = L.EPI_LORA | L.EPI_LORA_KR | L.EPI_DGELU | L.EPI_RANKOP | L.EPI_LGRAD | L.EPI_LNB_STAT
+        n1 = tiles(4 * w, w, f1, r)
+        n2 = tiles(w, 4 * w, L.EPI_LORA | L.EPI_LORA_KR | L.EPI_RANKOP | L.EPI_LNB_APPLY, r)
+        ln2_bwd = n1 if (0 < n1 <= 8 and n2 > 0) else 0
+    # ln_1's backward: row sums per head from ffm_attention_bwd_lnstat, FFM_EPI_LNB_APPLY on the plain panel tile of dX(qkv)
+    ln1_bwd = 0
+    if sw.lnb_fold and sw.lnb_fold1 and ln1 and 2 * heads <= 24 and ops.attention_bwd_lnstat_ok(tokens, causal, dtype):
+        if tiles(w, 3 * w, L.EPI_LNB_APPLY) > 0:
+            ln1_bwd = 2 * heads
+    return Route(ln1, ln2, lgrad, ln2_bwd, ln1_bwd, red_at)
+
+
 _PACKED = ("w_in", "w_in_t", "w_out", "w_out_t", "w_fc", "w_fc_t", "w_proj", "w_proj_t", "w_in_ln", "w_fc_ln")
 
 
@@ -232,20 +316,12 @@ class _Stack:
     """A transformer tower (vision with FairLoRA, or text) with its saved activations."""
 
     def __init__(self, width: int, heads: int, layers: int, tokens: int, max_images: int, causal: bool,
-                 rank: int, dtype, device, x3: bool = False):
+                 rank: int, dtype, device, sw: Switches, x3: bool = False):
         self.width, self.heads, self.layers, self.L = width, heads, layers, tokens
-        self.causal, self.rank, self.dtype = causal, rank, dtype
-        # FFM_TEXT_W16=1: the frozen weights of a float32 tower that runs beside a 16-bit vision tower (x3) as IEEE half in
-        # memory (FFM_F32_X3_W16) - see FairLoRAEngine.__init__; measured: no gain, off by default
-        self.wdtype = torch.float16 if (x3 and os.environ.get("FFM_TEXT_W16", "0") == "1") else dtype
+        self.causal, self.rank, self.dtype, self.sw = causal, rank, dtype, sw
+        self.routes: Dict[int, Route] = {}                   # rows -> tower_route (route())
         # x3: float32 tower whose products run on the bf16 matrix cores as hi/lo pairs (FFM_F32_X3)
         # (ops.gemm_nt is looked up per call: bench.py wraps it to time the launches)
-        # FFM_GELU_DERIV=1: the MLP's saved tensor is quick_gelu'(pre) instead of pre (ffm_gemm_args.gelu_deriv): the forward's
-        # epilogue has the sigmoid in hand and nothing but the dX product of c_proj reads the pre-activation.  Measured
-        # (round 4, serial rocprofv3 of one call each): dX(c_proj) 48.86 -> 48.48 us, c_fc forward 47.18 -> 48.43 us, the step
-        # 4.869 -> 4.874 ms (three alternating pairs): the backward epilogue is not bound by the derivative's exp + rcp, and
-        # the forward pays for the extra arithmetic.  Off by default; bit-identical in fp32 either way.
-        deriv = os.environ.get("FFM_GELU_DERIV", "0") == "1"
 
         # x3 (the text tower, 40 token rows): scratch for the products that are split over K across the grid
         # (ffm_gemm_args.sk_part, csrc/gemm_skinny.hip: N = 512 against K = 1536 / 2048 - c_proj forward, dX(c_fc), dX(qkv));
@@ -253,14 +329,12 @@ class _Stack:
         rows_max = max_images * tokens
         self.sk_part = None
         if x3 and rows_max <= 48:
-            need = max(ops.gemm_splitk_floats(rows_max, n_, k_, self.wdtype == torch.float16)
+            need = max(ops.gemm_splitk_floats(rows_max, n_, k_, False)
                        for n_, k_ in ((width, 4 * width), (width, 3 * width), (4 * width, width), (3 * width, width), (width, width)))
             if need > 0:
                 self.sk_part = torch.empty(need, device=device, dtype=torch.float32)
 
         def _gemm(*a, **k):
-            if deriv and (k.get("gelu_out") is not None or k.get("dgelu_aux") is not None):
-                k["gelu_deriv"] = True
             if self.sk_part is not None:
                 k["sk_part"] = self.sk_part
             return ops.gemm_nt(*a, x3=x3, **k)
@@ -283,16 +357,13 @@ class _Stack:
         self.act = [e(T, 4 * w) for _ in range(layers)]
         # partial row sums {sum, sum of squares} of every block input, left behind by its producer (FFM_EPI_ROWSTATS /
         # embed_lnpre) for the ln_1 that is folded into the qkv product: up to 8 column tiles
-        self.rowp = [f(8 * T * 2) for _ in range(layers + 1)] if (rank and _is16(dtype)) else None
-        self.rowp2 = [f(8 * T * 2) for _ in range(layers)] if (rank and _is16(dtype)) else None   # ... of xm (ln_2)
+        fold = _can_fold(rank, dtype)
+        self.rowp = [f(8 * T * 2) for _ in range(layers + 1)] if fold else None
+        self.rowp2 = [f(8 * T * 2) for _ in range(layers)] if fold else None   # ... of xm (ln_2)
         # ln_2's BACKWARD folded into dX(c_proj) / dX(c_fc) (FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY): the producer's partial row
-        # sums, consumed by the very next launch - one buffer per tower; rows -> column tiles of the producer (0: not folded)
+        # sums, consumed by the very next launch - one buffer per tower
         # (ln_1's: two partial rows per head from the attention backward kernels, consumed by dX(qkv))
-        self.lnb_part = f(max(8, 2 * heads) * T * 2) if (rank and _is16(dtype)) else None
-        self.foldb = {}
-        self.foldb1 = {}
-        self.fold = {}                                       # rows -> (np of the c_proj forward, ok) decision cache
-        self.fold2 = {}                                      # rows -> np of the out-proj forward (ln_2 into c_fc)
+        self.lnb_part = f(max(8, 2 * heads) * T * 2) if fold else None
         if rank:
             self.t1 = [f(T, rank) for _ in range(layers)]
             self.ts1 = [f(T, rank) for _ in range(layers)]
@@ -324,7 +395,13 @@ class _Stack:
                           "proj_A": f(ns * 4 * w * rank), "proj_B": f(ns * w * rank),
                           "fc_S": f(nb * 8 * rank), "proj_S": f(nb * 8 * rank)} for _ in range(layers)]
             self.plans = {}
-            self.lgrad = {}                                      # rows -> row tiles of the FFM_EPI_LGRAD partials (0: not served)
+
+    def route(self, rows: int) -> Route:
+        """Which fused kernels serve this tower at `rows` rows (decided once per row count, after the weights are loaded)."""
+        if rows not in self.routes:
+            self.routes[rows] = tower_route(self.width, self.heads, self.L, self.causal, self.rank, self.dtype,
+                                            self.blocks[0].packed is not None, rows, self.sw)
+        return self.routes[rows]
 
     def layer(self, i: int, rows: int) -> _LayerBufs:
         """Block i's share of the stash (everything the backward pass reads), cut to `rows`."""
@@ -355,7 +432,7 @@ class _InferWorkspace:
         f = lambda *s: torch.zeros(*s, device=dev, dtype=f32)
         self.xs = (e(T, w), e(T, w))
         self.xm, self.qkv, self.o, self.h, self.h2, self.act = e(T, w), e(T, 3 * w), e(T, w), e(T, w), e(T, w), e(T, 4 * w)
-        fold = bool(r) and _is16(dtype)                   # as _Stack: the partial row sums of the LayerNorm folds
+        fold = _can_fold(r, dtype)                        # the partial row sums of the LayerNorm folds
         self.rowps = (f(8 * T * 2), f(8 * T * 2)) if fold else None
         self.rowp2 = f(8 * T * 2) if fold else None
         # rank > 16: the down projections are launches of their own and t / ts their operands (one pair: c_fc's is dead
@@ -441,6 +518,17 @@ class FairLoRAEngine:
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.max_images = max_images
         v, t = cfg.vision, cfg.text
+        # what the tower hooks below and the step read: set before any of them runs
+        self.sw = Switches.from_env()
+        # FairLoRA down projections ride inside the GEMMs (FFM_EPI_RANKOP) when the rank fits one MFMA tile
+        self.fused_rank = 0 < cfg.lora.rank <= 16
+        self.pack_plan = None                         # rank operands of the fused products (_init_vision_late)
+        self._pack_event = None
+        self.pk_out: Dict[str, Tensor] = {}           # frozen weights outside the blocks in MFMA-fragment order
+        self.use_replay = True                        # replay recorded launch plans (host-side "graph")
+        # RN50: BatchNorm sums from its own pass instead of the producing GEMM's epilogue (diagnostics assign it) / the
+        # backward sums from the dX products
+        self.no_colstats, self.bn_bwd_fused = False, self.sw.bn_bwd_fused
         self.params = FlatParams(cfg, self.device)
         self.params.load(state_dict)
         self.n_text = cfg.n_prompts * cfg.n_cls
@@ -461,14 +549,8 @@ class FairLoRAEngine:
         # the tiny model (tools/auc_diag.py, AUC after equal rounds against the reference): text tower in bf16 0.0026 off,
         # f32 activations on bf16 weights 0.0020, all f32 0.0005.  Beside a bf16 vision tower the 40-row products run on
         # the bf16 matrix cores as hi/lo pairs (FFM_F32_X3, csrc/gemm_skinny.hip) instead of the 16x slower f32 MFMA.
-        # Round 4, FFM_TEXT_W16=1: the FROZEN weights of the tower as IEEE half (FFM_F32_X3_W16: 11 significant bits, what
-        # the reference's own PREC="fp16" holds, clip/model.py:609-630; split exactly into the bf16 hi + lo pair in the
-        # kernel), 151 instead of 302 MB of text weights per step beside the vision chain; activations, gradients and
-        # accumulation stay float32.  Measured (three alternating pairs, one call): 4.590 against 4.592 ms per step -
-        # with two column tiles per block the weights are not what the chain feels any more.
-        # Off by default: float32 weights.
         self.txt = _Stack(t.width, t.heads, t.layers, self.txt_len, self.n_text, True, 0, torch.float32, self.device,
-                          x3=(_is16(dtype)))
+                          self.sw, x3=(_is16(dtype)))
         dev, f32 = self.device, torch.float32
         self._init_vision(max_images)                 # tower-specific buffers (ViT here, RN50 in engine_rn.py)
         self.load_frozen(state_dict)
@@ -492,8 +574,8 @@ class FairLoRAEngine:
         # FFM_F16_GROWTH_INTERVAL (2000) good steps it doubles again, up to the initial value FFM_F16_GRAD_SCALE (4096).
         self.scale_state = None
         if dtype == torch.float16:
-            s0 = float(os.environ.get("FFM_F16_GRAD_SCALE", "4096"))
-            self.scale_state = torch.tensor([s0, 1.0 / s0, 1.0, 0.0, 0.0, s0, float(os.environ.get("FFM_F16_GROWTH_INTERVAL", "2000")), 1.0],
+            s0 = self.sw.f16_grad_scale
+            self.scale_state = torch.tensor([s0, 1.0 / s0, 1.0, 0.0, 0.0, s0, self.sw.f16_growth_interval, 1.0],
                                             device=dev, dtype=f32)
         self.dtbar = torch.zeros(cfg.n_cls, v.out_dim, device=dev, dtype=f32)
         self.attr_i32 = torch.zeros(max_images, device=dev, dtype=torch.int32)
@@ -518,7 +600,6 @@ class FairLoRAEngine:
             self.ot_tsum = torch.zeros(P, device=dev, dtype=f32)
             self.ot_dtn_part = torch.zeros(max_images * N * cfg.n_cls * v.out_dim, device=dev, dtype=f32)
         self.step_plans: Dict[tuple, list] = {}
-        self.use_replay = True                        # replay recorded launch plans (host-side "graph")
         # the two ends of the text tower (csrc/text.hip): absolute EOT row of every prompt, the un-normalised / normalised
         # text features, 1 / norm and ln_final's statistics kept for the way back, the projection's input gradient
         self.eot_rows = torch.tensor([i * self.txt_len + cfg.eot[i % cfg.n_cls] for i in range(self.n_text)],
@@ -543,7 +624,6 @@ class FairLoRAEngine:
         self.ev_text_bwd = torch.cuda.Event()
         self.ev_start = torch.cuda.Event()
         self.ev_pack = torch.cuda.Event()
-        self._pack_event = None
         self.max_infer_images = max_images if max_infer_images is None else int(max_infer_images)
         self._in_session = False
         self._init_infer()
@@ -551,7 +631,7 @@ class FairLoRAEngine:
     # ---------------------------------------------------- vision tower hooks --
     def _init_vision(self, max_images: int) -> None:
         cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
-        self.vis = _Stack(v.width, v.heads, v.layers, v.tokens, max_images, False, cfg.lora.rank, dtype, dev)
+        self.vis = _Stack(v.width, v.heads, v.layers, v.tokens, max_images, False, cfg.lora.rank, dtype, dev, self.sw)
         P = v.grid * v.grid
         self.cols = torch.zeros(max_images * P, 3 * v.patch * v.patch, device=dev, dtype=dtype)
         self.patch_out = torch.zeros(max_images * P, v.width, device=dev, dtype=dtype)
@@ -576,11 +656,6 @@ class FairLoRAEngine:
     def _init_vision_late(self) -> None:
         """After the frozen weights are loaded: the packed rank operands of the FairLoRA GEMMs."""
         cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
-        # FairLoRA down projections ride inside the GEMMs (FFM_EPI_RANKOP) when the rank fits one MFMA tile
-        self.fused_rank = 0 < cfg.lora.rank <= 16
-        # where a block's LoRA-gradient reductions start (_stack_backward); unset: by row count
-        self.red_at = int(os.environ["FFM_RED_AT"]) if "FFM_RED_AT" in os.environ else None
-        self.use_lgrad = os.environ.get("FFM_LGRAD", "1") != "0"    # the two large reductions inside the dX product of c_proj
         ie = "image_encoder.transformer.resblocks."
         self.sops = SOperands(self.params, [f"{ie}{i}.mlp.c_{n}." for i in range(v.layers) for n in ("fc", "proj")],
                               cfg, dev)
@@ -600,7 +675,7 @@ class FairLoRAEngine:
                     if _is16(dtype) else {}
                 self.lw_wide.append(wd)
                 for role, buf in pk.items():
-                    # ln_2's backward fold (_fold_ln2_bwd): the rank operand of dX(c_fc) carries W gamma and W beta + b as rows
+                    # ln_2's backward fold (Route.ln2_bwd): the rank operand of dX(c_fc) carries W gamma and W beta + b as rows
                     # 14 / 15 - its t[14] / t[15] are the two row sums against those vectors, out of the matrix cores; every
                     # consumer masks the slots beyond r (rank <= 14)
                     extra = (blk.c_fc, blk.d_fc) if (role == "fc_B" and _is16(dtype) and blk.c_fc is not None and cfg.lora.rank <= 14) else None
@@ -634,8 +709,8 @@ class FairLoRAEngine:
 
     def _load_stack(self, stack: _Stack, sd, prefix: str, lora: bool) -> None:
         old = stack.blocks if stack.blocks else None
-        W = lambda x: self._w(x, stack.wdtype)
-        WT = lambda x: self._wt(x, stack.wdtype)
+        W = lambda x: self._w(x, stack.dtype)
+        WT = lambda x: self._wt(x, stack.dtype)
         stack.blocks = []
         for i in range(stack.layers):
             p = f"{prefix}transformer.resblocks.{i}."
@@ -717,8 +792,7 @@ class FairLoRAEngine:
         put("proj_t", self._wt(sd[ie + "proj"]))                  # [out, width]: B operand of f = h proj
         # the three frozen weights outside the blocks in MFMA-fragment order too (16-bit modes): patch embedding and the
         # two products of the final projection take the panel kernel where their shape fills the chip
-        self.pk_out = getattr(self, "pk_out", {})
-        if _is16(self.dtype) and os.environ.get("FFM_PACK_OUT", "1") != "0":
+        if _is16(self.dtype) and self.sw.pack_out:
             for name in ("conv_w", "proj", "proj_t"):
                 w = getattr(self, name)
                 if w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0:
@@ -734,67 +808,6 @@ class FairLoRAEngine:
     def _dS(self, layer: int, which: str) -> Tensor:
         return self.sops.grad(f"image_encoder.transformer.resblocks.{layer}.mlp.c_{which}.")
 
-    def _fold_ln1(self, st: _Stack, rows: int) -> int:
-        """0: ln_1 runs as its own kernel.  Otherwise the number of partial row sums the c_proj forward of this row
-        count leaves per row (its column tiles): both that product and the qkv product are served by the panel kernel
-        with the folding epilogues (bf16, fused rank, frozen weights packed)."""
-        if st.rowp is None or not getattr(self, "fused_rank", False) or getattr(self, "no_ln_fold", False):
-            return 0
-        if rows not in st.fold:
-            w, r = st.width, st.rank
-            f_proj = L.EPI_BIAS | L.EPI_LORA | L.EPI_RESIDUAL | L.EPI_RANKOP | L.EPI_ROWSTATS
-            npj = ops.gemm_tiles_n(rows, w, 4 * w, f_proj, r, st.dtype, True)
-            nq = ops.gemm_tiles_n(rows, 3 * w, w, L.EPI_BIAS | L.EPI_LNIN, 0, st.dtype, True)
-            st.fold[rows] = npj if (npj > 0 and npj <= 8 and nq > 0) else 0
-        return st.fold[rows]
-
-    def _fold_ln2(self, st: _Stack, rows: int) -> int:
-        """The same for ln_2 in front of c_fc: partial row sums from the out-proj forward, the FairLoRA c_fc product with
-        the folding epilogue (its rank operand gamma-scaled), and dA(c_fc) from the raw rows (ffm_lora_grad_partial_ln)."""
-        if st.rowp2 is None or not getattr(self, "fused_rank", False) or getattr(self, "no_ln_fold", False):
-            return 0
-        if rows not in st.fold2:
-            w, r = st.width, st.rank
-            npo = ops.gemm_tiles_n(rows, w, w, L.EPI_BIAS | L.EPI_RESIDUAL | L.EPI_ROWSTATS, 0, st.dtype, True)
-            f_fc = L.EPI_BIAS | L.EPI_LORA | L.EPI_GELU | L.EPI_RANKOP | L.EPI_LNIN
-            nf = ops.gemm_tiles_n(rows, 4 * w, w, f_fc, r, st.dtype, True)
-            st.fold2[rows] = npo if (npo > 0 and npo <= 8 and nf > 0 and w % 128 == 0 and r <= 16) else 0
-        return st.fold2[rows]
-
-    def _fold_ln2_bwd(self, st: _Stack, rows: int, blk: _Block) -> int:
-        """ln_2's BACKWARD folded into the two dX products around it (round 6; include/ffm_hip.h FFM_EPI_LNB_*): 0 - the
-        LayerNorm backward runs as its own kernel; otherwise the column tiles of the dX product of c_proj, which leaves the
-        two row sums beside its FFM_EPI_LGRAD partial products, and the dX product of c_fc stores dL/d x_mid directly.
-        Needs the forward fold (its W gamma / W beta + b / A^T gamma / A^T beta vectors), the LGRAD epilogue and both
-        kernels for this row count.  FFM_LNB_FOLD=0: off (A/B runs)."""
-        if st.lnb_part is None or os.environ.get("FFM_LNB_FOLD", "1") == "0":
-            return 0
-        if rows not in st.foldb:
-            w, r = st.width, st.rank
-            n = 0
-            if self._fold_ln2(st, rows) and self._lgrad_rows(st, rows, blk) > 0 and r <= 14:
-                f1 = L.EPI_LORA | L.EPI_LORA_KR | L.EPI_DGELU | L.EPI_RANKOP | L.EPI_LGRAD | L.EPI_LNB_STAT
-                f2 = L.EPI_LORA | L.EPI_LORA_KR | L.EPI_RANKOP | L.EPI_LNB_APPLY
-                n1 = ops.gemm_tiles_n(rows, 4 * w, w, f1, r, st.dtype, True)
-                n2 = ops.gemm_tiles_n(rows, w, 4 * w, f2, r, st.dtype, True)
-                n = n1 if (0 < n1 <= 8 and n2 > 0) else 0
-            st.foldb[rows] = n
-        return st.foldb[rows]
-
-    def _fold_ln1_bwd(self, st: _Stack, rows: int) -> int:
-        """ln_1's BACKWARD folded into the attention backward (row sums per head: ffm_attention_bwd_lnstat) and the dX product
-        of the in-projection (FFM_EPI_LNB_APPLY on the plain panel tile): 0, or the number of partial rows (2 heads)."""
-        if st.lnb_part is None or os.environ.get("FFM_LNB_FOLD", "1") == "0" or os.environ.get("FFM_LNB_FOLD1", "1") == "0":
-            return 0
-        if rows not in st.foldb1:
-            w = st.width
-            n = 0
-            if self._fold_ln1(st, rows) and 2 * st.heads <= 24 and ops.attention_bwd_lnstat_ok(st.L, st.causal, st.dtype):
-                if ops.gemm_tiles_n(rows, w, 3 * w, L.EPI_LNB_APPLY, 0, st.dtype, True) > 0:
-                    n = 2 * st.heads
-            st.foldb1[rows] = n
-        return st.foldb1[rows]
-
     def _stack_forward(self, st: _Stack, rows: int, images: int, attr: Optional[Tensor], rows_per_sample: int,
                        bufs=None) -> Tensor:
         """The tower input is in layer 0's `x`; returns the tower output view.  bufs: the provider of every block's
@@ -805,6 +818,8 @@ class FairLoRAEngine:
         gemm = st.gemm
         bufs = st if bufs is None else bufs
         out = lb = None
+        rt = st.route(rows)
+        fold, fold2 = rt.ln1, rt.ln2
 
         def fc(a, w, **k):
             # c_fc + QuickGELU of the current block: pre-activation and activation (the backward reads both), or the
@@ -816,7 +831,6 @@ class FairLoRAEngine:
         for i, blk in enumerate(st.blocks):
             lb = bufs.layer(i, rows)
             x, xm, qkv, o, h, h2, act = lb.x, lb.xm, lb.qkv, lb.o, lb.h, lb.h2, lb.act
-            fold = self._fold_ln1(st, rows)
             if fold:
                 # ln_1 rides inside the qkv product: raw rows x gamma-scaled weight, normalised in the epilogue with the
                 # row sums the producer of x left behind (block 0: embed_lnpre, else the previous block's c_proj)
@@ -826,7 +840,6 @@ class FairLoRAEngine:
                 ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
                 gemm(h, blk.w_in, qkv, bias=blk.b_in, b_packed=blk.pk("w_in"))
             ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
-            fold2 = self._fold_ln2(st, rows) if r else 0
             gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=lb.rowp2 if fold2 else None)
             if not fold2:
                 ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, lb.st2[0], lb.st2[1])
@@ -871,6 +884,7 @@ class FairLoRAEngine:
         gemm = st.gemm
         g, g1 = st.g[:rows], st.g1[:rows]
         main = torch.cuda.current_stream(self.device)
+        rt = st.route(rows)
         for i in range(st.layers - 1, -1, -1):
             blk = st.blocks[i]
             x, xm = st.x[i][:rows], st.xm[i][:rows]
@@ -885,8 +899,7 @@ class FairLoRAEngine:
                 pt = st.part[i]
                 # ---- critical path: u = g B^T and dX (+ LoRA dx term), dS partials
                 fused = self.fused_rank
-                early = last and getattr(self, "tail_early", True)
-                if early:
+                if last:
                     # the step's tail: dB(c_proj) needs only gi and the forward's ts2 - it starts beside this block's dX
                     # product instead of behind it
                     self._ev_record(self.ev_tail0, main)
@@ -896,9 +909,9 @@ class FairLoRAEngine:
                 # FFM_EPI_LGRAD: dB(c_fc) = dpre^T ts1 and dA(c_proj) = act^T us2 leave with the dX product of c_proj, which
                 # holds dpre and (through pre) act in registers - per row tile, into the buffers the two reduction launches
                 # they replace would have filled (77 MB per block that the side stream no longer reads beside the chain)
-                lg = self._lgrad_rows(st, rows, blk) if fused else 0
+                lg = rt.lgrad
                 # ln_2's backward rides in this block's two dX products (not block 0 of a tower that stops there)
-                lnb = self._fold_ln2_bwd(st, rows, blk) if (fused and lg and not last) else 0
+                lnb = 0 if last else rt.ln2_bwd
                 if fused:
                     ro = ops.RankOp(self.rk[i]["proj_B"], self._S(i, "proj"), attr, rows_per_sample,
                                     lo.scaling, lo.lambda_group, ts_out=us2, t_fwd=st.t2[i][:rows], ds_part=pt["proj_S"],
@@ -933,8 +946,6 @@ class FairLoRAEngine:
                         self._ev_record(self.ev_tail, main)
                         self._ev_wait(self.grad_stream, self.ev_tail)
                         with self._on(self.grad_stream):
-                            if not early:
-                                ops.lora_grad_partial(gi, st.ts2[i][:rows], r, pt["proj_B"])
                             if not lg:
                                 ops.lora_grad_partial(act, us2, r, pt["proj_A"])
                                 ops.lora_grad_partial(dpre, st.ts1[i][:rows], r, pt["fc_B"])
@@ -952,7 +963,7 @@ class FairLoRAEngine:
                             if not lg:
                                 ops.lora_grad_partial(act, us2, r, pt["proj_A"])
                                 ops.lora_grad_partial(dpre, st.ts1[i][:rows], r, pt["fc_B"])
-                        if self._fold_ln2(st, rows):
+                        if rt.ln2:
                             ops.lora_grad_partial_ln(xm, us1, st.st2[i][0], st.st2[i][1], blk.ln2_w, blk.ln2_b, r, pt["fc_A"])
                         else:
                             ops.lora_grad_partial(h2, us1, r, pt["fc_A"])
@@ -964,11 +975,7 @@ class FairLoRAEngine:
                 # block's dX(c_fc) - beside its LayerNorm / out-proj / attention backward; 1: behind its attention backward;
                 # 2: behind the whole block - beside the NEXT block's two FairLoRA products, whose main loops live on
                 # LDS / L2 operands (the last block's have nothing behind them and always start at once)
-                # Measured (one call, alternating): configs[1] (6304 rows) 4.65-4.71 / 4.66-4.67 / 4.75-4.76 ms per step for
-                # 0 / 1 / 2; configs[3] (19 700 rows, rank 16: 52 MB of partials per block, whose sum took the attention
-                # backward beside it from 49 to 74 us) 12.45 / 12.42-12.46 / 12.37-12.38.
-                auto = 2 if rows > 12608 else 0
-                red_at = 0 if last or i == 0 else (auto if self.red_at is None else self.red_at)
+                red_at = 0 if last or i == 0 else rt.red_at
                 if red_at == 0:
                     reductions()
                 if last:
@@ -979,7 +986,7 @@ class FairLoRAEngine:
                 gout = st.g_l[i - 1][:rows] if i > 0 else g
             else:
                 gi, dpre, gout = g, st.dpre[:rows], g
-                lnb = 0
+                lnb = red_at = 0
                 gemm(gi, blk.w_proj_t, dpre, dgelu_aux=pre)
                 gemm(dpre, blk.w_fc_t, st.dh[:rows])
             if not lnb:
@@ -987,11 +994,11 @@ class FairLoRAEngine:
             gemm(g1, blk.w_out_t, st.do[:rows], b_packed=blk.pk("w_out_t"))
             # ln_1's backward: its two row sums leave with the attention backward (two partial rows per head), and the dX
             # product of the in-projection stores dL/d x = LayerNorm backward(g_h) + g1 directly
-            lnb1 = self._fold_ln1_bwd(st, rows) if r else 0
+            lnb1 = rt.ln1_bwd
             ops.attention_bwd(st.qkv[i][:rows], st.o[i][:rows], st.do[:rows], st.lse[i], st.delta, st.dqkv[:rows],
                               images, st.L, st.heads, st.causal,
                               ln_stat=(blk.c_in, blk.d_in, st.lnb_part) if lnb1 else None)
-            if r and red_at == 1:
+            if red_at == 1:
                 reductions()
             if lnb1:
                 gemm(st.dqkv[:rows], blk.w_in_t, gout, b_packed=blk.pk("w_in_t"),
@@ -999,7 +1006,7 @@ class FairLoRAEngine:
             else:
                 gemm(st.dqkv[:rows], blk.w_in_t, st.dh[:rows], b_packed=blk.pk("w_in_t"))
                 ops.layernorm_bwd(st.dh[:rows], x, blk.ln1_w, st.st1[i][0], st.st1[i][1], g1, gout)
-            if r and red_at == 2:
+            if red_at == 2:
                 reductions()
         if r:
             if self.sops.glob:
@@ -1008,44 +1015,27 @@ class FairLoRAEngine:
             self._ev_wait(main, self.ev_grads)
         return g
 
-    def _lgrad_rows(self, st: _Stack, rows: int, blk: _Block) -> int:
-        """Row tiles of the FFM_EPI_LGRAD partial products for this row count, 0 when the kernel that serves the dX product
-        of c_proj has no such epilogue (then the two reduction launches run) or FFM_LGRAD=0 asks for the launches."""
-        key = (rows, blk.packed is not None)
-        if key not in st.lgrad:
-            n = 0
-            deriv = os.environ.get("FFM_GELU_DERIV", "0") == "1"   # (the saved tensor is then gelu'(pre): no activation to recompute)
-            if self.use_lgrad and not deriv and blk.packed is not None and _is16(self.dtype) and st.rank % 4 == 0:
-                n = max(0, ops.gemm_lgrad_rows(rows, 4 * st.width, st.width, st.rank, self.dtype, True))
-                if n > ops.lora_grad_splits(rows):            # (the partial buffers are sized for the reduction kernel's splits)
-                    n = 0
-            st.lgrad[key] = n
-        return st.lgrad[key]
-
     def _reduce_plan(self, st: _Stack, rows: int, full_bwd: bool, layer: int):
         """Descriptor table (built once per row count and block) that sums the block's partials into params.grad."""
         key = (rows, full_bwd, layer)
         if key not in st.plans:
             r, G, w = st.rank, self.cfg.lora.num_groups, st.width
             nsp = ops.lora_grad_splits(rows)
-            ent = []
-            for li, (blk, pt) in enumerate(zip(st.blocks, st.part)):
-                if li != layer:
-                    continue
-                gv = lambda role: self.params.view(blk.lora[role], "grad")
-                # dS partial rows: GEMM row tiles when the down projection is fused, lora_down blocks otherwise
-                # (block 0's c_fc has no dX GEMM, so it always uses the stand-alone kernel)
-                # dS partial rows written by the dX GEMMs (c_proj: N = 4w, K = w; c_fc: N = w, K = 4w)
-                pk = st.blocks[li].packed is not None
-                nb_p = _ds_rows(rows, 4 * w, w, r, self.dtype, pk, dgelu=True) if self.fused_rank \
-                    else ops.lora_down_blocks(rows, w, r, self.dtype)
-                nb_f = _ds_rows(rows, w, 4 * w, r, self.dtype, pk) if (self.fused_rank and (li > 0 or full_bwd)) \
-                    else ops.lora_down_blocks(rows, 4 * w, r, self.dtype)
-                # (FFM_EPI_LGRAD: proj_A and fc_B hold one partial per row tile of the dX product of c_proj)
-                nlg = (self._lgrad_rows(st, rows, st.blocks[li]) if self.fused_rank else 0) or nsp
-                ent += [(pt["proj_S"], nb_p, G * r, self._dS(li, "proj"), 0, 0), (pt["fc_S"], nb_f, G * r, self._dS(li, "fc"), 0, 0),
-                        (pt["proj_B"], nsp, w * r, gv("proj_B"), w, r), (pt["proj_A"], nlg, 4 * w * r, gv("proj_A"), 0, 0),
-                        (pt["fc_B"], nlg, 4 * w * r, gv("fc_B"), 4 * w, r), (pt["fc_A"], nsp, w * r, gv("fc_A"), 0, 0)]
+            li, blk, pt = layer, st.blocks[layer], st.part[layer]
+            gv = lambda role: self.params.view(blk.lora[role], "grad")
+            # dS partial rows: GEMM row tiles when the down projection is fused, lora_down blocks otherwise
+            # (block 0's c_fc has no dX GEMM, so it always uses the stand-alone kernel)
+            # dS partial rows written by the dX GEMMs (c_proj: N = 4w, K = w; c_fc: N = w, K = 4w)
+            pk = blk.packed is not None
+            nb_p = _ds_rows(rows, 4 * w, w, r, self.dtype, pk, dgelu=True) if self.fused_rank \
+                else ops.lora_down_blocks(rows, w, r, self.dtype)
+            nb_f = _ds_rows(rows, w, 4 * w, r, self.dtype, pk) if (self.fused_rank and (li > 0 or full_bwd)) \
+                else ops.lora_down_blocks(rows, 4 * w, r, self.dtype)
+            # (FFM_EPI_LGRAD: proj_A and fc_B hold one partial per row tile of the dX product of c_proj)
+            nlg = st.route(rows).lgrad or nsp
+            ent = [(pt["proj_S"], nb_p, G * r, self._dS(li, "proj"), 0, 0), (pt["fc_S"], nb_f, G * r, self._dS(li, "fc"), 0, 0),
+                   (pt["proj_B"], nsp, w * r, gv("proj_B"), w, r), (pt["proj_A"], nlg, 4 * w * r, gv("proj_A"), 0, 0),
+                   (pt["fc_B"], nlg, 4 * w * r, gv("fc_B"), 4 * w, r), (pt["fc_A"], nsp, w * r, gv("fc_A"), 0, 0)]
             st.plans[key] = ops.ReducePlan(ent, self.device)
         return st.plans[key]
 
@@ -1199,14 +1189,13 @@ class FairLoRAEngine:
 
     def _pack_rank_operands(self) -> None:
         """ffm_lora_pack_multi over every adapter (one or two launches) on the CURRENT stream."""
-        plan = getattr(self, "pack_plan", None)
-        if plan is not None and getattr(self, "fused_rank", True):
-            plan.run()
+        if self.pack_plan is not None:                # (fused rank only)
+            self.pack_plan.run()
 
     def _rank_operands_ready(self) -> None:
         """In a training step the packing runs at the head of the side stream, beside the patch embedding (27 us off the
         main queue), and the vision chain waits for it here; outside a step (inference) it runs in line."""
-        ev = getattr(self, "_pack_event", None)
+        ev = self._pack_event
         if ev is None:
             self._pack_rank_operands()
         else:

@@ -14,8 +14,6 @@ flat parameter buffer, SGD, streams and launch-plan replay are the base class's.
 """
 from __future__ import annotations
 
-import os
-
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -79,10 +77,10 @@ class _Lora:
                       lo.lambda_group, self.t[:rows], self.ts[:rows])
         ops.gemm_nt(x, W, out, bias=bias, ts=self.ts[:rows], lw=e.params.view(self.kB), res=res, colstats=colstats)
 
-    def bwd(self, g: Tensor, Wt: Tensor, dx: Tensor, x: Tensor, attr: Optional[Tensor], rps: int, res=None,
-            defer: bool = False, bnbwd=None, colstats: Optional[Tensor] = None) -> None:
-        """g = dL/dy; writes dx = g W (+ LoRA term) (+ res) and the partial sums of dA, dB, dS (defer: the caller runs
-        grads() itself, on the gradient stream).  bnbwd / colstats (fused sites only): dx is the gradient of a BatchNorm
+    def bwd(self, g: Tensor, Wt: Tensor, dx: Tensor, attr: Optional[Tensor], rps: int, res=None,
+            bnbwd=None, colstats: Optional[Tensor] = None) -> None:
+        """g = dL/dy; writes dx = g W (+ LoRA term) (+ res) and the partial sums of dS; the caller runs grads() (dA, dB)
+        itself, on the gradient stream.  bnbwd / colstats (fused sites only): dx is the gradient of a BatchNorm
         output, and the product's epilogue leaves that BatchNorm's backward column sums in colstats (ops.gemm_nt)."""
         e, lo = self.eng, self.eng.cfg.lora
         rows = g.shape[0]
@@ -98,8 +96,6 @@ class _Lora:
             ops.lora_down(g, e.params.view(self.kB), True, S, attr, lo.rank, G, rps, lo.scaling,
                           lo.lambda_group, self.u[:rows], self.us[:rows], self.t[:rows] if self.fair else None, self.pS)
             ops.gemm_nt(g, Wt, dx, ts=self.us[:rows], lw=e.params.view(self.kA), lw_is_kr=True, res=res)
-        if not defer:
-            self.grads(g, x)
 
     def grads(self, g: Tensor, x: Tensor) -> None:
         """The rank-r reductions dB = g^T ts, dA = x^T us (partials); nothing downstream of them in the dX chain."""
@@ -277,12 +273,11 @@ class _Bneck:
         else:
             gid = self.gid[:ro]
         a = self.a2p[:ro] if self.stride > 1 else self.a2[:ri]
-        side = getattr(e, "grads_on_side", True)
         # stride 1: conv3's dX product writes the gradient of relu(bn2(.)) itself - its epilogue leaves bn2's backward column
         # sums of its row tiles behind (FFM_EPI_BNBWD), and bn2's backward skips its pass over dy / x / mask (13 of RN50's 16
         # blocks; FFM_BN_BWD_FUSED=0: A/B runs)
-        t2 = e.stat_rows(ri) if (self.stride == 1 and self.c3.fused and getattr(e, "bn_bwd_fused", True)) else 0
-        self.c3.bwd(self.dz3[:ro], W[p + "w3t"], self.da2p[:ro], a, attr, Ho * Ho, defer=side,
+        t2 = e.stat_rows(ri) if (self.stride == 1 and self.c3.fused and e.bn_bwd_fused) else 0
+        self.c3.bwd(self.dz3[:ro], W[p + "w3t"], self.da2p[:ro], attr, Ho * Ho,
                     bnbwd=(self.z2[:ri], self.a2[:ri], self.bn2.mean, self.bn2.rstd) if t2 else None,
                     colstats=e.stat_buf[0] if t2 else None)
         da2 = self.da2p[:ro]
@@ -293,7 +288,7 @@ class _Bneck:
         # dX = conv3x3(dY; w') is the gradient of relu(bn1(.)): the same for bn1 where the convolution is not split over K
         # (conv3x3 returns the partial rows it wrote: one per 128-row tile, or - launches split over K, layer3 / layer4 -
         # one per 8 / 32 rows from the split-K reduction kernel; 0 only where that would exceed 4096 partial rows)
-        fuse1 = e.stat_rows(ri) > 0 and getattr(e, "bn_bwd_fused", True)
+        fuse1 = e.stat_rows(ri) > 0 and e.bn_bwd_fused
         t1 = ops.conv3x3(self.dz2[:ri], W[p + "w2b"], self.da1[:ri], images, Hi, Hi, e.zero16, e.splitk,
                          colstats=e.stat_buf[0] if fuse1 else None,
                          bnbwd=(self.z1[:ri], self.a1[:ri], self.bn1.mean, self.bn1.rstd) if fuse1 else None)
@@ -302,23 +297,21 @@ class _Bneck:
             e._ev_wait(main, self.ev_d[3])                        # join: the downsample branch's input gradient
         # this block's dX IS dL/d(output) of the block in front of it: its bn3's backward sums (and, for an identity-skip
         # block, the masked gradient it passes on) leave with this product's epilogue
-        t3 = e.stat_rows(ri) if (consumer is not None and self.c1.fused and getattr(e, "bn_bwd_fused", True)) else 0
-        self.c1.bwd(self.dz1[:ri], W[p + "w1t"], self.dx[:ri], x, attr, Hi * Hi, res=gid, defer=side,
+        t3 = e.stat_rows(ri) if (consumer is not None and self.c1.fused and e.bn_bwd_fused) else 0
+        self.c1.bwd(self.dz1[:ri], W[p + "w1t"], self.dx[:ri], attr, Hi * Hi, res=gid,
                     bnbwd=(consumer.z3[:ri], consumer.out[:ri], consumer.bn3.mean, consumer.bn3.rstd,
                            None if consumer.has_down else consumer.gid[:ri]) if t3 else None,
                     colstats=e.stat_buf[0] if t3 else None)
-        if side:
-            # off the dX chain: this block's four rank-r reductions (every operand is a per-block buffer that stays put
-            # until the next step's forward)
-            main = torch.cuda.current_stream(e.device)
-            e._ev_record(self.ev, main)
-            e._ev_wait(e.grad_stream, self.ev)
-            with e._on(e.grad_stream):
-                self.c3.grads(self.dz3[:ro], a)
-                self.c1.grads(self.dz1[:ri], x)
-                # ... and the sum of this block's partials behind them (round 4: ONE launch for every site of the trunk at the
-                # end of the backward pass sat in the step's tail for 92 us - layer1's sites alone have 784 partial rows)
-                self.reduce_plan(images).run()
+        # off the dX chain: this block's four rank-r reductions (every operand is a per-block buffer that stays put
+        # until the next step's forward)
+        e._ev_record(self.ev, main)
+        e._ev_wait(e.grad_stream, self.ev)
+        with e._on(e.grad_stream):
+            self.c3.grads(self.dz3[:ro], a)
+            self.c1.grads(self.dz1[:ri], x)
+            # ... and the sum of this block's partials behind them (round 4: ONE launch for every site of the trunk at the
+            # end of the backward pass sat in the step's tail for 92 us - layer1's sites alone have 784 partial rows)
+            self.reduce_plan(images).run()
         return self.dx[:ri], t3
 
     def reduce_plan(self, images: int) -> "ops.ReducePlan":
@@ -357,7 +350,6 @@ class RN50Engine(FairLoRAEngine):
         self.rnw: Dict[str, Tensor] = {}
         self.bns: List[_BN] = []
         self.bn_scratch = self.bn_cmax = self.stat_scratch = 0
-        self.bn_bwd_fused = os.environ.get("FFM_BN_BWD_FUSED", "1") != "0"      # _Bneck.backward: bn2's sums from conv3's dX product
         self.bn_training = False
         self.pack_entries: list = []
         e = lambda rows, C: torch.zeros(rows, C, device=dev, dtype=dt)
@@ -417,7 +409,6 @@ class RN50Engine(FairLoRAEngine):
             raise NotImplementedError(self.cfg.lora.lora_type)    # trainers/GLP_OT_SVLoRA.py:561-567: ResNet knows FairLoRA only
         self.sops = SOperands(self.params, [site.prefix for blk in self.blocks for site, _ in blk.loras()], self.cfg,
                               self.device)
-        self.fused_rank = 0 < self.cfg.lora.rank <= 16
         self.pack_plan = ops.PackPlan(self.pack_entries, self.dtype, self.device) if self.fused_rank else None
 
     def _n_layer_events(self) -> int:
@@ -546,7 +537,7 @@ class RN50Engine(FairLoRAEngine):
         """Row tiles of the 128x128 GEMM over `rows` rows when its epilogue should leave the BatchNorm column sums behind
         (training mode, at most 4096 partial rows: ffm_bn_fwd's limit); else 0."""
         t = (rows + 127) // 128
-        return t if (self.bn_training and 0 < t <= 4096 and not getattr(self, "no_colstats", False)) else 0
+        return t if (self.bn_training and 0 < t <= 4096 and not self.no_colstats) else 0
 
     def _vision_forward(self, b: int, S: int, has_attr: bool, wait=None) -> None:
         cfg, v, W = self.cfg, self.cfg.vision, self.rnw
@@ -587,25 +578,23 @@ class RN50Engine(FairLoRAEngine):
         rows = b * L
         a32 = self.attr_i32[:b] if has_attr else None
         tok, qkv, dqkv = self.tok[:rows], self.qkv[:rows], self.dqkv[:rows]
-        side = getattr(self, "grads_on_side", True)
-        self.ap["c"].bwd(self.dfeat[:rows], W["ap_ct"], self.d_o[:rows], self.att_o[:rows], None, L, defer=side)
+        self.ap["c"].bwd(self.dfeat[:rows], W["ap_ct"], self.d_o[:rows], None, L)
         ops.attention_bwd(qkv, self.att_o[:rows], self.d_o[:rows], self.lse, self.delta, dqkv, b, L, v.heads, False)
         acc = None
         for i, n in enumerate("qkv"):
             dst = self.dtok[i & 1][:rows]
-            self.ap[n].bwd(dqkv[:, i * E:(i + 1) * E], W[f"ap_{n}t"], dst, tok, None, L, res=acc, defer=side)
+            self.ap[n].bwd(dqkv[:, i * E:(i + 1) * E], W[f"ap_{n}t"], dst, None, L, res=acc)
             acc = dst
-        if side:
-            # the attention pool's eight rank-r reductions beside the trunk's dX chain (dfeat, att_o, dqkv and tok stay
-            # put until the next step)
-            main = torch.cuda.current_stream(self.device)
-            self._ev_record(self.ev_ap, main)
-            self._ev_wait(self.grad_stream, self.ev_ap)
-            with self._on(self.grad_stream):
-                self.ap["c"].grads(self.dfeat[:rows], self.att_o[:rows])
-                for i, n in enumerate("qkv"):
-                    self.ap[n].grads(dqkv[:, i * E:(i + 1) * E], tok)
-                self._reduce(b, "ap").run()
+        # the attention pool's eight rank-r reductions beside the trunk's dX chain (dfeat, att_o, dqkv and tok stay
+        # put until the next step)
+        main = torch.cuda.current_stream(self.device)
+        self._ev_record(self.ev_ap, main)
+        self._ev_wait(self.grad_stream, self.ev_ap)
+        with self._on(self.grad_stream):
+            self.ap["c"].grads(self.dfeat[:rows], self.att_o[:rows])
+            for i, n in enumerate("qkv"):
+                self.ap[n].grads(dqkv[:, i * E:(i + 1) * E], tok)
+            self._reduce_ap(b).run()
         g = self.dx4[:b * HW]
         ops.attnpool_tokens(acc, None, g, b, HW, backward=True)
         t3 = 0
@@ -620,39 +609,28 @@ class RN50Engine(FairLoRAEngine):
         ops.avgpool2(g, dsa[2], b, H1, H1, backward=True)
         self.sbn[2].bwd(dsa[2], sa[2], sz[2], dsz[2])
         # (the stem's two 3x3 dX products feed a BatchNorm backward each: its column sums leave with them, as in the blocks)
-        fs = self.stat_rows(r1) > 0 and getattr(self, "bn_bwd_fused", True)
+        fs = self.stat_rows(r1) > 0 and self.bn_bwd_fused
         for k, wn in ((1, "s3b"), (0, "s2b")):
             tk = ops.conv3x3(dsz[k + 1], W[wn], dsa[k], b, H1, H1, self.zero16, colstats=self.stat_buf[0] if fs else None,
                              bnbwd=(sz[k], sa[k], self.sbn[k].mean, self.sbn[k].rstd) if fs else None)
             self.sbn[k].bwd(dsa[k], sa[k], sz[k], dsz[k], part=self.stat_buf[0], part_rows=tk if fs else 0)
-        if getattr(self, "grads_on_side", True):
-            # the partial sums of every site -> params.grad, behind the reductions on the gradient stream
-            main = torch.cuda.current_stream(self.device)
-            self._ev_record(self.ev_layer[0], main)
-            self._ev_wait(self.grad_stream, self.ev_layer[0])
-            # (every block and the attention pool have summed their partials behind their own reductions by now)
-            if self.sops.glob:
-                self._glue(self.sops.finish, self.grad_stream)
-            self._ev_record(self.ev_grads, self.grad_stream)
-            self._ev_wait(main, self.ev_grads)
-        else:
-            self._reduce(b).run()
-            if self.sops.glob:
-                self._glue(self.sops.finish)
+        # the partial sums of every site -> params.grad, behind the reductions on the gradient stream
+        self._ev_record(self.ev_layer[0], main)
+        self._ev_wait(self.grad_stream, self.ev_layer[0])
+        # (every block and the attention pool have summed their partials behind their own reductions by now)
+        if self.sops.glob:
+            self._glue(self.sops.finish, self.grad_stream)
+        self._ev_record(self.ev_grads, self.grad_stream)
+        self._ev_wait(main, self.ev_grads)
 
-    def _reduce(self, b: int, what: str = "all") -> "ops.ReducePlan":
-        """what: 'all' (every site, one launch: the arrangement without a gradient stream) or 'ap' (the attention pool's)."""
-        if (b, what) not in self.rn_plans:
-            v = self.cfg.vision
+    def _reduce_ap(self, b: int) -> "ops.ReducePlan":
+        """Sums the partials of the attention pool's four sites into params.grad."""
+        if b not in self.rn_plans:
             ent = []
-            if what == "all":
-                for blk in self.blocks:
-                    for site, H in blk.loras():
-                        ent += site.reduce_entries(b * H * H)
             for n in "qkvc":
-                ent += self.ap[n].reduce_entries(b * v.tokens)
-            self.rn_plans[(b, what)] = ops.ReducePlan(ent, self.device)
-        return self.rn_plans[(b, what)]
+                ent += self.ap[n].reduce_entries(b * self.cfg.vision.tokens)
+            self.rn_plans[b] = ops.ReducePlan(ent, self.device)
+        return self.rn_plans[b]
 
     # -------------------------------------------------------------------- API --
     def _step_body(self, b: int, S: int, has_attr: bool) -> None:

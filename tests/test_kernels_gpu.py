@@ -871,7 +871,7 @@ def panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, dt, before_check
     n2 = ops.gemm_tiles_n(M, K, N, 2 | 4 | 64 | 4096, r, dt, True)
     if tn <= 0 or nlg <= 0 or n2 <= 0:
         pytest.skip("no FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY kernel pair for this shape or tile mask (the engine then launches "
-                    "ffm_layernorm_bwd: FairLoRAEngine._fold_ln2_bwd asks the same two questions)")
+                    "ffm_layernorm_bwd: the engine's route, Route.ln2_bwd, asks the same two questions)")
     g = lambda *sh, **k: rnd(*sh, **k)
     # the LayerNorm-folded forward product: pre = LN(x) W_eff^T + b
     x = g(M, K, dt=dt, seed=301)
