@@ -991,30 +991,19 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
         if (!off || dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) return ffm_skinny_launch(a, dtype, s);
     }
     if (dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) return FFM_EUNSUP;      // split-operand products: skinny shapes only
-    if (a.flags & (FFM_EPI_LNB_STAT | FFM_EPI_LNB_APPLY)) {              // LayerNorm backward folded in: one panel tile each
+    if (a.flags & (FFM_EPI_LNB_STAT | FFM_EPI_LNB_APPLY)) {              // LayerNorm backward folded in: its arguments
         if ((a.flags & FFM_EPI_LNB_STAT) && !a.lnb_part) return FFM_EINVAL;
         if ((a.flags & FFM_EPI_LNB_APPLY) && rk && a.rank > 14) return FFM_EUNSUP;   // rows 14 / 15 of rk carry W gamma and d
         if ((a.flags & FFM_EPI_LNB_APPLY) && (!a.lnb_part || a.lnb_np <= 0 || a.lnb_np > (rk ? 8 : 24) || !a.lnb_x || ((uintptr_t)a.lnb_x & 15) ||
                                              !a.lnb_gamma || !a.ln_mean || !a.ln_rstd || (rk && !a.ln_rk) || !a.res || ((uintptr_t)a.res & 15)))
             return FFM_EINVAL;
-        const int cfgn = (a.b_packed && !a.colstat_part) ? ffm_panel_select(a.M, a.N, a.K, a.flags, a.rank, dtype, true) : -1;
-        return cfgn >= 0 ? ffm_panel_launch(a, cfgn, s) : FFM_EUNSUP;
     }
-    if (a.flags & FFM_EPI_LGRAD) {                                        // gradient partial products: one panel tile only
-        const int cfgg = (a.b_packed && !a.colstat_part) ? ffm_panel_select(a.M, a.N, a.K, a.flags, a.rank, dtype, true) : -1;
-        return cfgg >= 0 ? ffm_panel_launch(a, cfgg, s) : FFM_EUNSUP;
-    }
-    if (a.flags & (FFM_EPI_ROWSTATS | FFM_EPI_LNIN)) {                    // LayerNorm folding: the panel kernel only
-        if (a.colstat_part) return FFM_EUNSUP;                            // ... which has no column-sum epilogue
-        const int cfgl = a.b_packed ? ffm_panel_select(a.M, a.N, a.K, a.flags, a.rank, dtype, true) : -1;
-        return cfgl >= 0 ? ffm_panel_launch(a, cfgl, s) : FFM_EUNSUP;
-    }
-    // column sums (colstat_part) are an epilogue of the 128x128 / 128xN kernels only: a packed weight does not send
-    // such a launch to the panel kernel, which would return without writing them
-    if (a.b_packed && !a.colstat_part) {
-        const int cfg = ffm_panel_select(a.M, a.N, a.K, a.flags, a.rank, dtype, true);
-        if (cfg >= 0) return ffm_panel_launch(a, cfg, s);
-    }
+    // The panel kernel needs the packed weight.  Column sums (colstat_part) are an epilogue of the 128x128 / 128xN kernels
+    // only: a packed weight does not send such a launch to the panel kernel, which would return without writing them
+    const int cfg = (a.b_packed && !a.colstat_part) ? ffm_panel_select(a.M, a.N, a.K, a.flags, a.rank, dtype, true) : -1;
+    if (cfg >= 0) return ffm_panel_launch(a, cfg, s);
+    // LayerNorm folding, its backward and the gradient partial products: epilogues of the panel kernel only
+    if (a.flags & (FFM_EPI_LNB_STAT | FFM_EPI_LNB_APPLY | FFM_EPI_LGRAD | FFM_EPI_ROWSTATS | FFM_EPI_LNIN)) return FFM_EUNSUP;
     const int fl = a.flags & ~FFM_EPI_RANKOP;
     // BatchNorm-backward column sums exist in the kernels instantiated with the bit only (cases below; rank <= 16)
     if ((fl & FFM_EPI_BNBWD) && !(rk && (fl & ~FFM_EPI_RESIDUAL) == (FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_BNBWD)) && fl != FFM_EPI_BNBWD) return FFM_EUNSUP;
@@ -1471,29 +1460,40 @@ static int conv3x3_impl(const void* x, const void* w, void* y, int B, int H, int
     return FFM_OK;
 }
 
+// The host queries: which kernel ffm_gemm_nt would launch for this product, and its tile (128x128, 8 waves per CU: this file's)
+static ffm_panel_tile query_tile(int M, int N, int K, int flags, int rank, int dtype, int packed, int* cfg) {
+    *cfg = ffm_panel_select(M, N, K, flags, rank, dtype, packed != 0);
+    return *cfg >= 0 ? ffm_panel_tile_of(FFM_PANEL_CFGS[*cfg]) : ffm_panel_tile{BM, BN, 8};
+}
+
+// rows of dS partials (panel kernel: tiles_m x tiles_n, every block owns a slice of its tile row)
 extern "C" int ffm_gemm_tiles_m(int M, int N, int K, int flags, int rank, int dtype, int packed) {
-    const int cfg = ffm_panel_select(M, N, K, flags, rank, dtype, packed != 0);
-    return cfg >= 0 ? ffm_panel_ds_rows(M, N, cfg) : (M + BM - 1) / BM;
+    int cfg;
+    const ffm_panel_tile t = query_tile(M, N, K, flags, rank, dtype, packed, &cfg);
+    return (M + t.bm - 1) / t.bm * (cfg >= 0 ? N / t.bn : 1);
 }
 
 extern "C" int ffm_gemm_lgrad_rows(int M, int N, int K, int flags, int rank, int dtype, int packed) {
-    const int cfg = ffm_panel_select(M, N, K, flags | FFM_EPI_LGRAD, rank, dtype, packed != 0);
-    return cfg >= 0 ? (M + 16 * FFM_PANEL_CFGS[cfg].mf - 1) / (16 * FFM_PANEL_CFGS[cfg].mf) : FFM_EUNSUP;
+    int cfg;
+    const ffm_panel_tile t = query_tile(M, N, K, flags | FFM_EPI_LGRAD, rank, dtype, packed, &cfg);
+    return cfg >= 0 ? (M + t.bm - 1) / t.bm : FFM_EUNSUP;
 }
 
+// column tiles (rows of rowstat_part under FFM_EPI_ROWSTATS)
 extern "C" int ffm_gemm_tiles_n(int M, int N, int K, int flags, int rank, int dtype, int packed) {
-    const int cfg = ffm_panel_select(M, N, K, flags, rank, dtype, packed != 0);
-    if (cfg >= 0) return ffm_panel_tiles_n(N, cfg);
-    if (flags & (FFM_EPI_ROWSTATS | FFM_EPI_LNIN | FFM_EPI_LNB_STAT | FFM_EPI_LNB_APPLY)) return FFM_EUNSUP;
-    return (N + BN - 1) / BN;
+    int cfg;
+    const ffm_panel_tile t = query_tile(M, N, K, flags, rank, dtype, packed, &cfg);
+    if (cfg < 0 && (flags & (FFM_EPI_ROWSTATS | FFM_EPI_LNIN | FFM_EPI_LNB_STAT | FFM_EPI_LNB_APPLY))) return FFM_EUNSUP;
+    return (N + t.bn - 1) / t.bn;
 }
 
 extern "C" int ffm_gemm_tile_shape(int M, int N, int K, int flags, int rank, int dtype, int packed, int32_t* shape3) {
-    const int cfg = ffm_panel_select(M, N, K, flags, rank, dtype, packed != 0);
+    int cfg;
+    const ffm_panel_tile t = query_tile(M, N, K, flags, rank, dtype, packed, &cfg);
     if (shape3) {
-        shape3[0] = cfg >= 0 ? 16 * FFM_PANEL_CFGS[cfg].mf : BM;
-        shape3[1] = cfg >= 0 ? ffm_panel_bn(FFM_PANEL_CFGS[cfg]) : BN;
-        shape3[2] = cfg >= 0 ? FFM_PANEL_CFGS[cfg].pw * FFM_PANEL_CFGS[cfg].per_cu : 8;      // waves per CU
+        shape3[0] = t.bm;
+        shape3[1] = t.bn;
+        shape3[2] = t.waves;
     }
     return cfg;
 }

@@ -1,5 +1,8 @@
-// Panel GEMM: kernel selection, the plain / bias / residual instantiations and the load-time weight packer.
-// (kernel: gemm_panel_impl.h; FairLoRA epilogues: gemm_panel_rk.hip)
+// Panel GEMM: kernel selection, the instantiations of the plain rows and the load-time weight packer.
+// (kernel: gemm_panel_impl.h; the FairLoRA rows: gemm_panel_rk*.hip)
+// What tiles and epilogues exist is written in gemm_panel.h alone: the selector below adds the conditions on run-time
+// arguments, the switches and the cost model; ffm_panel_launch instantiates the plain rows (`unit` 0 of the table).
+// Enabling a masked row by default is its bit in FFM_PANEL_MASK_DEFAULT.
 #include "gemm_panel_impl.h"
 #include <cstdlib>
 
@@ -32,42 +35,6 @@ __global__ __launch_bounds__(256) void pack_b_kernel(const bf16_t* __restrict__ 
     }
 }
 
-// plain epilogues the panel kernel is instantiated for (PANEL_CASE below)
-bool plain_flags_ok(int flags) {
-    switch (flags) {
-        case 0:
-        case FFM_EPI_BIAS:
-        case FFM_EPI_BIAS | FFM_EPI_RESIDUAL:
-        case FFM_EPI_BIAS | FFM_EPI_RESIDUAL | FFM_EPI_ROWSTATS:      // out-proj forward leaving row sums for ln_2
-        case FFM_EPI_BIAS | FFM_EPI_LNIN:                              // qkv forward with ln_1 folded in
-        case FFM_EPI_LNB_APPLY: return true;                           // dX of qkv applying ln_1's backward
-    }
-    return false;
-}
-
-bool rk_flags_ok(int flags, int rank) {
-    if (rank <= 0 || rank > 16) return false;
-    if (flags & FFM_EPI_LNB_APPLY)                             // LayerNorm backward applied: the dX epilogue of c_fc only
-        return (flags & ~FFM_EPI_RANKOP) == (FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_LNB_APPLY) && rank <= 14;   // (rows 14 / 15 of rk: W gamma, d)
-    if (flags & FFM_EPI_LGRAD) {                               // the gradient partial products: the dX epilogue of c_proj only
-        // (... which may also leave LayerNorm-backward row sums: FFM_EPI_LNB_STAT rides on the LGRAD epilogue)
-        if ((flags & ~(FFM_EPI_RANKOP | FFM_EPI_LNB_STAT)) != (FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU | FFM_EPI_LGRAD) || rank % 4) return false;
-        return true;
-    }
-    if (flags & FFM_EPI_LNB_STAT) return false;
-    if ((flags & FFM_EPI_LNIN) && (flags & ~(FFM_EPI_RANKOP | FFM_EPI_LNIN)) != (FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU))
-        return false;                                          // ln_2 folded in: the c_fc forward epilogue only
-    if ((flags & FFM_EPI_ROWSTATS) && (flags & ~(FFM_EPI_RANKOP | FFM_EPI_ROWSTATS)) != (FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL))
-        return false;                                          // row sums: the c_proj forward epilogue only
-    switch (flags & ~(FFM_EPI_RANKOP | FFM_EPI_ROWSTATS | FFM_EPI_LNIN)) {
-        case FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU:
-        case FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL:
-        case FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU:
-        case FFM_EPI_LORA | FFM_EPI_LORA_KR: return true;
-    }
-    return false;
-}
-
 }  // namespace
 
 // Cost model (both kernels are bound by the bytes a CU pulls through its texture path): rounds x operand rows
@@ -78,16 +45,18 @@ int ffm_panel_select(int M, int N, int K, int flags, int rank, int dtype, bool p
     flags &= ~FFM_EPI_GELU_ONLY;
     if (!packed || dtype != FFM_BF16 || K % 128 != 0 || K < 512) return -1;
     const bool rk = (flags & FFM_EPI_RANKOP) != 0;
-    if (rk ? !rk_flags_ok(flags, rank) : !plain_flags_ok(flags)) return -1;
+    // FairLoRA epilogues: rank rows 0..15 of rk; with FFM_EPI_LNB_APPLY rows 14 / 15 carry W gamma and d; the gradient
+    // partial products of FFM_EPI_LGRAD go four rank rows at a time
+    if (rk && (rank <= 0 || rank > 16 || ((flags & FFM_EPI_LNB_APPLY) && rank > 14) || ((flags & FFM_EPI_LGRAD) && rank % 4))) return -1;
+    flags &= ~FFM_EPI_RANKOP;
     // FFM_PANEL=off: always the 128x128 kernel (A/B runs); read once per process, not per launch
     static const bool panel_off = [] {
         const char* f = getenv("FFM_PANEL");
         return f && (f[0] == 'o' || f[0] == '0');
     }();
     if (panel_off) return -1;
-    // Configurations 5 and up are enabled by a bit mask (default FFM_PANEL_MASK_DEFAULT; FFM_PANEL_MASK=<int> overrides, A/B
-    // runs): 5 = 176x128 FairLoRA two waves per SIMD, 6 = 160x128 plain ditto, 7 = 208x384 FairLoRA ditto, 8 = 160x128
-    // FairLoRA, 9 = 240x256 plain, 10 = 240x256 plain two waves per SIMD, 11 / 12 = 160x128 FairLoRA / plain with the K split
+    // The rows marked `masked` in FFM_PANEL_CFGS are enabled by bit <index> of a mask (default FFM_PANEL_MASK_DEFAULT;
+    // FFM_PANEL_MASK=<int> overrides, A/B runs)
     static const int exp_mask = [] {
         const char* f = getenv("FFM_PANEL_MASK");
         return f ? atoi(f) : FFM_PANEL_MASK_DEFAULT;
@@ -97,18 +66,12 @@ int ffm_panel_select(int M, int N, int K, int flags, int rank, int dtype, bool p
     int pick = -1;
     for (int c = 0; c < FFM_PANEL_NCFG; ++c) {
         const ffm_panel_cfg& cf = FFM_PANEL_CFGS[c];
-        const int bm = 16 * cf.mf, bn = ffm_panel_bn(cf), nfe = bn / 64;      // nfe: the tile's width in 64-column units
-        if (N % bn || cf.rankop != rk) continue;
-        if (c >= 5 && !((exp_mask >> c) & 1)) continue;
-        if (c == 5 || c == 6 || c == 9) continue;              // measured in round 3, lost, no longer instantiated
-        if (cf.ks && K % 256) continue;                       // the K-split loop is unrolled by four K64 steps
-        if ((flags & FFM_EPI_LGRAD) && c != 7) continue;      // instantiated for the 8-wave 208x384 tile only
-        if ((flags & FFM_EPI_LNB_APPLY) && c != (rk ? 8 : 2)) continue;  // ... and for the 4-wave 160x128 tiles only
-        if ((flags & FFM_EPI_ROWSTATS) && ((2 * cf.nf) & (2 * cf.nf - 1))) continue;   // row sums: power-of-two lanes per row
-        // measured (tools/bench_panel.py): with a plain epilogue and a short K the 256-wide tile does not pay for the
-        // un-overlapped prologue / store burst of a single round (qkv, K = 768: 34.6 us against 32.5 us)
+        const ffm_panel_tile t = ffm_panel_tile_of(cf);
+        const int bm = t.bm, bn = t.bn, nfe = bn / 64;      // nfe: the tile's width in 64-column units
+        if (N % bn || cf.rankop != rk || !ffm_panel_has(c, flags)) continue;
+        if (cf.masked && !((exp_mask >> c) & 1)) continue;
+        if (K < cf.min_k || (cf.ks && K % 256)) continue;     // (the K-split loop is unrolled by four K64 steps)
         const int per_cu = cf.per_cu;
-        if (!rk && nfe >= 4 && K < 1536 && per_cu == 1 && c < 5) continue;
         const long blocks = (long)((M + bm - 1) / bm) * (N / bn);
         // more than one round of tiles loses to the 128x128 kernel, whose two blocks per CU overlap one tile's epilogue
         // with the other's main loop (qkv at bs 32: 720 blocks of 160x128, 36.9 us against 32.5 us)
@@ -125,41 +88,14 @@ int ffm_panel_select(int M, int N, int K, int flags, int rank, int dtype, bool p
     return pick;
 }
 
-int ffm_panel_ds_rows(int M, int N, int cfg) {
-    const int bm = 16 * FFM_PANEL_CFGS[cfg].mf, bn = ffm_panel_bn(FFM_PANEL_CFGS[cfg]);
-    return ((M + bm - 1) / bm) * (N / bn);
-}
-
-int ffm_panel_tiles_n(int N, int cfg) { return N / ffm_panel_bn(FFM_PANEL_CFGS[cfg]); }
-
-#define PANEL_CASE(F)                                                                      \
-    case F:                                                                                \
-        switch (cfg) {                                                                     \
-            case 1: return ffm_panel::launch_panel<16, 4, false, F>(a, s);                 \
-            case 2: return ffm_panel::launch_panel<10, 2, false, F>(a, s);                 \
-            case 4: return ffm_panel::launch_panel<8, 4, false, F>(a, s);                  \
-            case 10: return ffm_panel::launch_panel<15, 2, false, F, 8>(a, s);             \
-            case 12: return ffm_panel::launch_panel<10, 2, false, F, 8, 1>(a, s);          \
-        }                                                                                  \
-        return FFM_EINVAL;
-
+// the plain rows; the FairLoRA ones: gemm_panel_rk*.hip
 int ffm_panel_launch(const ffm_gemm_args& a, int cfg, hipStream_t s) {
     if (((uintptr_t)a.b_packed & 15) || a.ldc % 8) return FFM_EINVAL;
     if ((a.flags & FFM_EPI_ROWSTATS) && !a.rowstat_part) return FFM_EINVAL;
     if ((a.flags & FFM_EPI_LNIN) && (!a.ln_part || !a.ln_c || a.ln_np <= 0 || a.ln_np > 8 || !a.bias)) return FFM_EINVAL;
     if ((a.flags & FFM_EPI_LNIN) && (a.flags & FFM_EPI_RANKOP) && !a.ln_rk) return FFM_EINVAL;
     if (a.flags & FFM_EPI_RANKOP) return ffm_panel_launch_rk(a, cfg, s);
-    switch (a.flags) {
-        PANEL_CASE(0)
-        PANEL_CASE(FFM_EPI_BIAS)
-        PANEL_CASE(FFM_EPI_BIAS | FFM_EPI_RESIDUAL)
-        PANEL_CASE(FFM_EPI_BIAS | FFM_EPI_RESIDUAL | FFM_EPI_ROWSTATS)
-        PANEL_CASE(FFM_EPI_BIAS | FFM_EPI_LNIN)
-        case FFM_EPI_LNB_APPLY:                                        // dX of the in-projection applying ln_1's backward
-            if (cfg == 2) return ffm_panel::launch_panel<10, 2, false, FFM_EPI_LNB_APPLY>(a, s);
-            return FFM_EINVAL;
-    }
-    return FFM_EINVAL;
+    return ffm_panel::launch_unit<0>(a, cfg, s);
 }
 
 extern "C" int ffm_pack_b(const void* src, void* dst, int N, int K, int ld, void* stream) {

@@ -1357,4 +1357,39 @@ int launch_panel(const ffm_gemm_args& a, hipStream_t s) {
     return FFM_OK;
 }
 
+// configuration C with epilogue F: the template arguments are the table's
+template <int C, int F> int launch_cfg(const ffm_gemm_args& a, hipStream_t s) {
+    constexpr ffm_panel_cfg cf = FFM_PANEL_CFGS[C];
+    if constexpr (ffm_panel_has(C, F))
+        return launch_panel<cf.mf, cf.nf, cf.rankop, F, cf.pw, cf.ks>(a, s);
+    else
+        return FFM_EINVAL;
+}
+
+// configuration C with the epilogue a.flags asks for: instantiates every kernel of row C
+template <int C> int launch_row(const ffm_gemm_args& a, hipStream_t s) {
+#define FFM_PANEL_LAUNCH(W)                            \
+    case (W): return launch_cfg<C, (W)>(a, s);         \
+    case (W) | FFM_EPI_GELU_ONLY: return launch_cfg<C, (W) | FFM_EPI_GELU_ONLY>(a, s);
+    if constexpr (FFM_PANEL_CFGS[C].rankop) {
+        switch (a.flags & ~FFM_EPI_RANKOP) { FFM_PANEL_EPI_RK(FFM_PANEL_LAUNCH) }
+    } else {
+        switch (a.flags) { FFM_PANEL_EPI_PLAIN(FFM_PANEL_LAUNCH) }
+    }
+#undef FFM_PANEL_LAUNCH
+    return FFM_EINVAL;
+}
+
+// configuration cfg, if it is a built row whose `unit` is U: translation unit U calls this once and so instantiates
+// exactly its rows.  FFM_EINVAL for every other index.
+template <int U, int C = 0> int launch_unit(const ffm_gemm_args& a, int cfg, hipStream_t s) {
+    if constexpr (C < FFM_PANEL_NCFG) {
+        if constexpr (FFM_PANEL_CFGS[C].built && FFM_PANEL_CFGS[C].unit == U)
+            if (cfg == C) return launch_row<C>(a, s);
+        return launch_unit<U, C + 1>(a, cfg, s);
+    } else {
+        return FFM_EINVAL;
+    }
+}
+
 }  // namespace ffm_panel
