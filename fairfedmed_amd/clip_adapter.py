@@ -78,12 +78,41 @@ def geometry_from_clip(sd: Dict[str, Tensor]) -> Tuple[object, C.TextCfg]:
     return vision, text
 
 
+def resize_positional_embedding(pos: Tensor, grid_new: int) -> Tensor:
+    """A ViT's positional embedding [1 + g * g, w] for a grid_new x grid_new patch grid, fp32: the class row is kept, the
+    patch rows are resampled as a [g, g, w] image (bicubic, align_corners=False) - the usual way to run a CLIP ViT at
+    another input size.  The same grid returns the same values bit for bit.  An extension beyond the reference."""
+    pos = pos.detach().float()
+    g = round((pos.shape[0] - 1) ** 0.5)
+    assert pos.dim() == 2 and g * g + 1 == pos.shape[0], f"positional embedding of {pos.shape[0]} rows is not 1 + g * g"
+    if grid_new == g:
+        return pos.clone()
+    if grid_new <= 0:
+        raise ValueError(f"grid {grid_new}")
+    img = pos[1:].reshape(1, g, g, -1).permute(0, 3, 1, 2)                 # [1, w, g, g]
+    img = torch.nn.functional.interpolate(img, size=(grid_new, grid_new), mode="bicubic", align_corners=False)
+    return torch.cat([pos[:1], img.permute(0, 2, 3, 1).reshape(grid_new * grid_new, -1)], 0)
+
+
+def vision_for_input(cfg, vision):
+    """The checkpoint's vision geometry at cfg.INPUT.SIZE.  Equal sizes: unchanged.  Otherwise the reference's assertion
+    (trainers/GLP_OT_SVLoRA.py:79) stands unless cfg.INPUT.INTERPOLATE_POS opts into a ViT at another input size (a multiple
+    of the patch; the positional embedding is resized when the weights are loaded)."""
+    size = int(cfg.INPUT.SIZE[0])
+    if size == vision.image_size:
+        return vision
+    assert getattr(cfg.INPUT, "INTERPOLATE_POS", False), \
+        f"cfg_imsize ({size}) must equal to clip_imsize ({vision.image_size})"                     # :79
+    if not isinstance(vision, C.VisionCfg):
+        raise NotImplementedError("INPUT.INTERPOLATE_POS: ViT towers only")
+    return C.with_image_size(vision, size)
+
+
 def model_cfg_from_reference(cfg, classnames: Sequence[str], clip_sd: Dict[str, Tensor], tokens: Tensor) -> C.ModelCfg:
     """ModelCfg from the reference's config tree (the fields CustomCLIP.__init__ / build_model read) + CLIP's shapes."""
     vision, text = geometry_from_clip(clip_sd)
     got, lora = cfg.TRAINER.GLP_OT, getattr(cfg.TRAINER, "GLP_OT_LORA", None)
-    assert cfg.INPUT.SIZE[0] == vision.image_size, \
-        f"cfg_imsize ({cfg.INPUT.SIZE[0]}) must equal to clip_imsize ({vision.image_size})"       # :79
+    vision = vision_for_input(cfg, vision)
     # The other prompt variants of PromptLearner (trainers/GLP_OT_SVLoRA.py:84-175) are not merely unused by the FairLoRA
     # scripts: with this trainer's N prompts they do not run in the reference either.  CTX_INIT leaves a 2-D ctx that
     # forward() permutes as 4-D (:133-136); CSC allocates ctx [n_cls, n_ctx, d] and views it as [N * n_cls, ...]
@@ -144,6 +173,8 @@ def state_dict_from_clip(mcfg: C.ModelCfg, clip_sd: Dict[str, Tensor], tokens: T
             t = lora_s_init(lo.rank, lo.num_groups)                        # 'same+cycle' (:402-417)
         elif key.endswith("lora_S.weight") or key.endswith("lora_S_global.weight"):
             t = torch.linspace(1, 0.1, steps=lo.rank)                      # :294-304, 418-422
+        elif key == "image_encoder.positional_embedding":
+            t = resize_positional_embedding(clip_sd["visual.positional_embedding"], mcfg.vision.grid)   # INPUT.INTERPOLATE_POS
         elif key.startswith("image_encoder."):
             t = clip_sd["visual." + key[len("image_encoder."):].replace(".original_linear.", ".")]
         elif key.startswith("text_encoder.transformer."):

@@ -134,29 +134,40 @@ class ModelCfg:
         return asdict(self)
 
 
-def vit_b16(rank: int = 8, alpha: float = 2.0, num_groups: int = 3) -> ModelCfg:
-    """CLIP ViT-B/16 FairLoRA (BASELINE.json configs[1..3])."""
-    return ModelCfg(lora=LoraCfg(rank=rank, alpha=alpha, num_groups=num_groups))
+def with_image_size(vision: VisionCfg, image_size: int) -> VisionCfg:
+    """The same ViT at another input size (a whole number of patches): only the token count changes.  An extension beyond
+    the reference, which fixes the input at CLIP's own size (trainers/GLP_OT_SVLoRA.py:79)."""
+    if image_size <= 0 or image_size % vision.patch:
+        raise ValueError(f"image size {image_size} is not a positive multiple of the patch size {vision.patch}")
+    import dataclasses
+    return dataclasses.replace(vision, image_size=image_size)
 
 
-def vit_tiny(rank: int = 4, alpha: float = 2.0, num_groups: int = 3) -> ModelCfg:
+def vit_b16(rank: int = 8, alpha: float = 2.0, num_groups: int = 3, image_size: int = 224) -> ModelCfg:
+    """CLIP ViT-B/16 FairLoRA (BASELINE.json configs[1..3]).  image_size other than CLIP's 224 (384: 577 tokens) goes
+    with a resized positional embedding (clip_adapter.resize_positional_embedding)."""
+    return ModelCfg(vision=with_image_size(VisionCfg(), image_size), lora=LoraCfg(rank=rank, alpha=alpha, num_groups=num_groups))
+
+
+def vit_tiny(rank: int = 4, alpha: float = 2.0, num_groups: int = 3, image_size: int = 64) -> ModelCfg:
     """A small geometry with the same structure, for fast parity tests:
     64x64 image, 16 patches + cls = 17 tokens, width 128 (2 heads of 64),
     2 vision layers; text width 128 (2 heads), 2 layers, context 77 (the
-    reference's tokenizer always pads prompts to 77, clip/clip.py:180-220)."""
+    reference's tokenizer always pads prompts to 77, clip/clip.py:180-220).
+    image_size 272 / 336: 290 / 442 tokens, the streaming attention kernels' side of 256."""
     return ModelCfg(
-        vision=VisionCfg(image_size=64, patch=16, width=128, layers=2, heads=2, out_dim=128),
+        vision=VisionCfg(image_size=image_size, patch=16, width=128, layers=2, heads=2, out_dim=128),
         text=TextCfg(context_length=77, width=128, heads=2, layers=2),
         lora=LoraCfg(rank=rank, alpha=alpha, num_groups=num_groups),
         eot=(9, 8),
     )
 
 
-def vit_tiny_3d(rank: int = 4, dim_per_3d_slice: int = 4, num_groups: int = 3) -> ModelCfg:
+def vit_tiny_3d(rank: int = 4, dim_per_3d_slice: int = 4, num_groups: int = 3, image_size: int = 64) -> ModelCfg:
     """vit_tiny with the 3D OCT front end (DATASET.MODALITY_TYPE 'oct_bscans'): every group of
     `dim_per_3d_slice` B-scans goes through the trainable 5x5 conv (trainers/GLP_OT_SVLoRA.py:634-639)."""
     import dataclasses
-    return dataclasses.replace(vit_tiny(rank=rank, num_groups=num_groups), dim_per_3d_slice=dim_per_3d_slice)
+    return dataclasses.replace(vit_tiny(rank=rank, num_groups=num_groups, image_size=image_size), dim_per_3d_slice=dim_per_3d_slice)
 
 
 def rn50(rank: int = 8, alpha: float = 8.0, num_groups: int = 2) -> ModelCfg:

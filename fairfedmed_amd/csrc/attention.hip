@@ -1,5 +1,6 @@
 // Multi-head self-attention, head_dim 64, whole key range per workgroup
-// (L <= 256: 197 vision tokens, 77 text tokens), MFMA 16x16.
+// (L <= 256: 197 vision tokens, 77 text tokens), MFMA 16x16.  Longer sequences go to the streaming kernels of
+// attention_long.hip (the two entry points at the end of this file decide).
 //
 // Orientation: scores are computed transposed, S^T = K Q^T, so a lane holds one
 // query column (q = lane & 15) and 4 consecutive keys per 16-key fragment
@@ -1101,12 +1102,16 @@ int dispatch_bwd(int nfp, const void* qkv, const void* out, const void* dout, co
 int ffm_attn3_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int dtype, hipStream_t s);
 int ffm_attn3_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int L, int heads,
                   int dtype, hipStream_t s, const float* ln_wg, const float* ln_d, float* ln_part);
+// attention_long.hip: L > 256, every storage type, with and without the mask (dtype: the caller's real code)
+int ffm_attn_long_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int causal, int dtype, hipStream_t s);
+int ffm_attn_long_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int L,
+                      int heads, int causal, int dtype, hipStream_t s);
 
 extern "C" int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int causal,
                                  int dtype, void* stream) {
     if (!qkv || !out || B <= 0 || L <= 0 || heads <= 0) return FFM_EINVAL;
-    if (L > 256) return FFM_EUNSUP;
     if (((uintptr_t)qkv | (uintptr_t)out) & 15) return FFM_EINVAL;
+    if (L > 256) return ffm_attn_long_fwd(qkv, out, lse, B, L, heads, causal, dtype, (hipStream_t)stream);
     const int nfp = (((L + 15) / 16) + 1) & ~1;
     hipStream_t s = (hipStream_t)stream;
     if ((dtype == FFM_BF16 || dtype == FFM_F16) && !causal && attn3_allowed()) {
@@ -1131,8 +1136,8 @@ extern "C" int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, 
 extern "C" int ffm_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                                  void* dqkv, int B, int L, int heads, int causal, int dtype, void* stream) {
     if (!qkv || !out || !dout || !lse || !delta || !dqkv || B <= 0 || L <= 0 || heads <= 0) return FFM_EINVAL;
-    if (L > 256) return FFM_EUNSUP;
     if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) & 15) return FFM_EINVAL;
+    if (L > 256) return ffm_attn_long_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, dtype, (hipStream_t)stream);
     const int nfp = (((L + 15) / 16) + 1) & ~1;
     hipStream_t s = (hipStream_t)stream;
     if ((dtype == FFM_BF16 || dtype == FFM_F16) && !causal && attn3_allowed()) {

@@ -97,6 +97,10 @@ def build_parser() -> argparse.ArgumentParser:
     a("--synthetic", action="store_true", help="synthetic batches instead of the dataset under --root")
     a("--synthetic-batches", type=int, default=4)
     a("--transport", type=str, default="uint8", choices=["uint8", "float32"])
+    a("--input_size", type=int, default=0, help="INPUT.SIZE = (N, N); 0 keeps the configuration's (224)")
+    a("--interpolate_pos", action="store_true",
+      help="INPUT.INTERPOLATE_POS: run a ViT at an INPUT.SIZE other than its checkpoint's (a multiple of the patch size) with "
+           "the positional embedding resized (bicubic) at load - an extension: the reference asserts the two sizes equal")
     a("--compat-sequential-optimizer", action="store_true")
     a("--save-trainable-only", action="store_true",
       help="global_client{idx}_final.pth without the frozen CLIP tensors (the reference saves the full state_dict)")
@@ -128,7 +132,7 @@ def setup_cfg(args) -> NS:
     cfg = NS(
         SEED=args.seed, OUTPUT_DIR=args.output_dir, VERBOSE=True,
         INPUT=NS(SIZE=(224, 224), PIXEL_MEAN=list(C.CLIP_PIXEL_MEAN), PIXEL_STD=list(C.CLIP_PIXEL_STD),
-                 NO_TRANSFORM=args.input_no_transform),
+                 NO_TRANSFORM=args.input_no_transform, INTERPOLATE_POS=args.interpolate_pos),
         DATASET=NS(NAME="FairFedMed", ROOT=args.root, USERS=args.num_users, ATTRIBUTE_TYPE=args.attribute_type,
                    ATTRIBUTES=list(args.attributes), MODALITY_TYPE=args.modality_type,
                    DIM_PER_3D_SLICE=args.dim_per_3d_slice),
@@ -159,6 +163,9 @@ def setup_cfg(args) -> NS:
         args.lr, args.stepsize, args.round, args.gamma, 1
     cfg.DATALOADER.TRAIN_X.BATCH_SIZE = getattr(cfg.DATALOADER.TRAIN_X, "BATCH_SIZE", args.train_batch_size)
     cfg.TEST.BATCH_SIZE = getattr(getattr(cfg.DATALOADER, "TEST", NS()), "BATCH_SIZE", args.test_batch_size)
+    if args.input_size:
+        cfg.INPUT.SIZE = (args.input_size, args.input_size)
+    cfg.INPUT.INTERPOLATE_POS = bool(args.interpolate_pos or getattr(cfg.INPUT, "INTERPOLATE_POS", False))
     if args.backbone:
         cfg.MODEL.BACKBONE.NAME = args.backbone
     if args.trainer:
@@ -209,7 +216,11 @@ def main(argv: Optional[List[str]] = None, log=print, cfg_hook=None):
         base = C.rn50() if cfg.MODEL.BACKBONE.NAME in ("RN50", "rn50") else C.vit_b16()
         from .trainer import ATTRIBUTE_GROUPS
         G = len(ATTRIBUTE_GROUPS[cfg.DATASET.NAME][args.attribute_type])
-        mcfg = C.ModelCfg(vision=base.vision, text=base.text, lora=C.LoraCfg(rank=args.lora_rank, alpha=args.lora_alpha,
+        vision = base.vision
+        if cfg.INPUT.INTERPOLATE_POS:                       # synthetic images at INPUT.SIZE, as the trainer's model expects
+            from .clip_adapter import vision_for_input
+            vision = vision_for_input(cfg, vision)
+        mcfg = C.ModelCfg(vision=vision, text=base.text, lora=C.LoraCfg(rank=args.lora_rank, alpha=args.lora_alpha,
                                                                             num_groups=G),
                           n_prompts=args.num_prompt, n_ctx=args.n_ctx,
                           dim_per_3d_slice=args.dim_per_3d_slice if is3d else 0)

@@ -200,7 +200,13 @@ class GLP_OT_SVLoRA:
             else getattr(cfg.MODEL, "GEOMETRY")
         # 3D modalities go through the trainable per-slice conv (trainers/GLP_OT_SVLoRA.py:584-586)
         is_3d = getattr(cfg.DATASET, "MODALITY_TYPE", "slo_fundus") in MODALITIES_3D
-        return C.ModelCfg(vision=base.vision, text=base.text,
+        vision = base.vision
+        if getattr(cfg.INPUT, "INTERPOLATE_POS", False):
+            # an extension beyond the reference (which fixes the input at CLIP's size): the ViT at INPUT.SIZE, its positional
+            # embedding resized in build_model
+            from .clip_adapter import vision_for_input
+            vision = vision_for_input(cfg, vision)
+        return C.ModelCfg(vision=vision, text=base.text,
                           lora=C.LoraCfg(rank=lora.RANK, alpha=lora.ALPHA, num_groups=G, lora_type=lora.TYPE,
                                          global_s=bool(getattr(lora, "GLOBAL_S", False))),
                           n_prompts=cfg.TRAINER.GLP_OT.N, n_ctx=cfg.TRAINER.GLP_OT.N_CTX, n_cls=len(names), eot=eot,
@@ -218,6 +224,11 @@ class GLP_OT_SVLoRA:
         if sd is None:
             # pretrained CLIP cannot be downloaded here (trainers/GLP_OT_SVLoRA.py:23-43 needs network)
             sd = synth.make_state_dict(mcfg, seed=getattr(cfg, "SEED", 1), lora_init="reference")
+        pos = "image_encoder.positional_embedding"
+        if getattr(cfg.INPUT, "INTERPOLATE_POS", False) and pos in sd and sd[pos].shape[0] != mcfg.vision.tokens:
+            from .clip_adapter import resize_positional_embedding
+            sd = type(sd)(sd)                                           # the caller's checkpoint stays as it is
+            sd[pos] = resize_positional_embedding(sd[pos], mcfg.vision.grid)
         bs = max(cfg.DATALOADER.TRAIN_X.BATCH_SIZE, cfg.TEST.BATCH_SIZE)
         if mcfg.dim_per_3d_slice:
             # every sample becomes C / DIM_PER_3D_SLICE ViT images; the volume depth comes from the data

@@ -400,14 +400,20 @@ int ffm_attnpool_tokens(const void* in, const void* pos, void* out, int B, int H
  * packed in-projection produces them (clip/model.py:352).  out: [B*L, heads*64].
  * lse: [B, heads, L] fp32 log-sum-exp of the scaled scores (saved for backward); NULL: not stored (a forward-only
  * pass - every kernel behind this entry point skips the store, `out` is the same).
+ * Any L: up to 256 tokens a workgroup holds the whole key range in LDS (16-bit, unmasked, 65..256 tokens:
+ * csrc/attention3.hip; every other such shape: csrc/attention.hip); beyond 256 the keys are streamed through LDS in
+ * 64-key tiles with an online softmax (csrc/attention_long.hip: fp32 / bf16 / half, with and without the mask).  Every
+ * output element is summed by one wave in a fixed order in all of them: the bits do not depend on B or on the grid.
  */
 int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads,
                       int causal, int dtype, void* stream);
 
 /*
  * Backward of the above: given dout, recomputes P from qkv and lse and writes
- * dqkv [B*L, 3*heads*64].  delta: [B, heads, L] fp32, unused (the row sums
- * of dO * O are formed inside the kernels since ABI 3); kept so that callers need not change.
+ * dqkv [B*L, 3*heads*64].  delta: [B, heads, L] fp32 scratch (the row sums of dO * O are formed inside the kernels
+ * since ABI 3; the 16-bit kernels of csrc/attention3.hip and the streaming kernels for L > 256 hand them from their dQ
+ * launch to their dK/dV launch through it, on `stream`).  Any L, served as the forward is; two launches (dQ, then dK/dV),
+ * no atomics and no sum across workgroups.
  */
 int ffm_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
                       float* delta, void* dqkv, int B, int L, int heads, int causal,
@@ -418,7 +424,7 @@ int ffm_attention_bwd(const void* qkv, const void* out, const void* dout, const 
  * frozen): ln_part [2 heads][B L][2] fp32 <- {sum_n dqkv[n] ln_wg[n], sum_n dqkv[n] (qkv[n] - ln_d[n])} over 64-column
  * slices - slot h: the q columns of head h, slot heads + h: its k and v columns; ln_wg = W gamma, ln_d = W beta + b of the
  * LayerNorm-folded in-projection [3 heads 64].  The dX product of qkv then takes them as FFM_EPI_LNB_APPLY's lnb_part with
- * lnb_np = 2 heads (<= 24).  16-bit storage, no mask, 97..256 tokens only: ffm_attention_bwd_lnstat_ok says whether a
+ * lnb_np = 2 heads (<= 24).  16-bit storage, no mask, 97..256 tokens only (the streaming kernels for L > 256 do not leave them): ffm_attention_bwd_lnstat_ok says whether a
  * shape is served (1) or ffm_attention_bwd_lnstat returns FFM_EUNSUP (0).
  */
 int ffm_attention_bwd_lnstat_ok(int L, int causal, int dtype);
