@@ -11,7 +11,9 @@ Readers for the two benchmarks' on-disk layouts, mirroring ``FairFedMedDataset``
 ``__getitem__`` returns what the reference returns: (float32 [C,H,W] raw 0..255, label int64, attrs int64 [n_attr]).
 ``raw(item)`` returns the same sample in its TRANSPORT form: uint8, before the float conversion and the channel
 repeat (1 channel for SLO fundus / chest X-ray), 12x fewer bytes over PCIe; the engine expands it on the GPU
-(``ffm_expand_u8``), bit-identically, because uint8 -> float32 is exact.
+(``ffm_expand_u8``), bit-identically, because uint8 -> float32 is exact.  ``raw(item, native=True)`` is the stored uint8
+sample BEFORE the resize: transport="native" ships a ragged ``NativeBatch`` of those with the tap tables of ``resize_taps`` and
+the engine resizes on the GPU (``ffm_resize_u8``).
 
 scikit-image is not in this image: ``resize_image`` restates ``skimage.transform.resize`` (order 1, mode 'reflect',
 no anti-aliasing when enlarging, clip to the input range) on scipy.ndimage.zoom - parity for the resize branch is
@@ -50,6 +52,141 @@ def resize_image(img: np.ndarray, shape) -> np.ndarray:
     out = ndi.zoom(src, factors, order=1, mode="mirror", grid_mode=True)
     out = np.clip(out, img.min(), img.max())
     return out.astype(out_dtype)
+
+
+def _mirror(i: np.ndarray, n: int) -> np.ndarray:
+    """scipy.ndimage's 'mirror' for integer indices: reflection about the centre of the edge sample, period 2n - 2."""
+    if n == 1:
+        return np.zeros_like(i)
+    p = 2 * n - 2
+    i = np.mod(i, p)
+    return np.where(i >= n, p - i, i)
+
+
+_TAPS: Dict[tuple, tuple] = {}
+NATIVE_MAX_TAPS = 32                                      # FFM_RESIZE_MAX_TAPS (include/ffm_hip.h)
+
+
+def resize_taps(n_in: int, n_out: int):
+    """One axis of ``resize_image`` as a matrix A [n_out, n_in], float64, in its sparse form: (start int32 [n_out],
+    w float64 [n_out, T]) with A[o, start[o] + t] = w[o, t] and zero elsewhere, start[o] + T <= n_in.
+
+    A = Z G.  G [n_in, n_in] is ndimage.gaussian_filter1d(sigma = (n_in / n_out - 1) / 2, truncate 4, mode 'mirror') when the
+    axis shrinks, else the identity.  Z [n_out, n_in] is ndimage.zoom(order 1, grid_mode=True, mode 'mirror'): output o
+    reads the source coordinate (o + 1/2) n_in / n_out - 1/2, reflected into [0, n_in - 1] about the centres of the edge
+    samples, and interpolates linearly between its two neighbours.  Rows sum to 1, weights are >= 0, the non-zeros of a
+    row are one contiguous run (T = 1 for n_in == n_out: the identity; 2 when enlarging).  Cached per (n_in, n_out)."""
+    key = (int(n_in), int(n_out))
+    if key in _TAPS:
+        return _TAPS[key]
+    n, R = key
+    if n < 1 or R < 1:
+        raise ValueError(f"resize_taps({n_in}, {n_out})")
+    G = np.eye(n)
+    f = R / n
+    if f < 1:
+        sigma = max(0.0, (1 / f - 1) / 2)
+        if sigma > 1e-15:
+            lw = int(4.0 * sigma + 0.5)
+            k = np.arange(-lw, lw + 1)
+            phi = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+            phi /= phi.sum()
+            G = np.zeros((n, n))
+            rows = np.repeat(np.arange(n), k.size)
+            np.add.at(G, (rows, _mirror(rows + np.tile(k, n), n)), np.tile(phi, n))
+    Z = np.zeros((R, n))
+    if n == 1:
+        Z[:, 0] = 1.0
+    else:
+        cc = (np.arange(R) + 0.5) * (n / R) - 0.5
+        p = 2.0 * (n - 1)
+        cc = np.mod(cc, p)
+        cc = np.where(cc > n - 1, p - cc, cc)                          # 'mirror' of the coordinate itself
+        i0 = np.floor(cc).astype(np.int64)
+        t = cc - i0
+        o = np.arange(R)
+        np.add.at(Z, (o, _mirror(i0, n)), 1.0 - t)
+        np.add.at(Z, (o, _mirror(i0 + 1, n)), t)
+    A = Z @ G
+    nz = A > 0
+    first = nz.argmax(1)
+    last = n - 1 - nz[:, ::-1].argmax(1)
+    T = int((last - first + 1).max())
+    start = np.minimum(first, n - T).astype(np.int32)
+    w = np.ascontiguousarray(A[np.arange(R)[:, None], start[:, None] + np.arange(T)[None, :]])
+    start.setflags(write=False)
+    w.setflags(write=False)
+    _TAPS[key] = (start, w)
+    return _TAPS[key]
+
+
+class NativeBatch:
+    """A ragged batch of stored uint8 samples and the resize that makes it a [B, C1 * rep, R, R] float32 batch on the GPU
+    (ffm_resize_u8 through ops.resize_u8; the engines accept it where they accept an image tensor).
+
+        pix    uint8 [bytes]          all planes of all images back to back; image b is [C1, H_b, W_b]
+        geom   int32 [B, 4]           byte offset in pix, H_b, W_b, table id
+        start  int32 [NG * 2 * R]     per distinct (H, W) of the batch and axis (0: rows over H, 1: columns over W)
+        w      fp32  [NG, 2, R, T]    resize_taps of that axis, zero-padded to the batch's widest run T
+        C1, rep, R, T                 planes per image, channel repeat, output size, taps
+        sizes                         ((H_b, W_b), ...) on the host (checks without a device read)"""
+
+    def __init__(self, pix, geom, start, w, C1: int, rep: int, R: int, sizes):
+        self.pix, self.geom, self.start, self.w = pix, geom, start, w
+        self.C1, self.rep, self.R, self.T, self.sizes = int(C1), int(rep), int(R), int(w.shape[-1]), tuple(sizes)
+
+    @classmethod
+    def from_planes(cls, samples: Sequence[np.ndarray], rep: int, R: int) -> "NativeBatch":
+        """samples: uint8 arrays [C1, H_b, W_b].  A sample with H_b == R is one the readers do not resize (the decision is
+        the readers' own, by height alone), so its width must be R as well: the ValueError an engine gives such a batch."""
+        C1 = samples[0].shape[0]
+        ids: Dict[tuple, int] = {}
+        geom, off = [], 0
+        for s in samples:
+            if s.dtype != np.uint8 or s.ndim != 3 or s.shape[0] != C1:
+                raise TypeError("NativeBatch takes uint8 samples [C1, H, W] with one C1")
+            h, wd = s.shape[1:]
+            if h == R and wd != R:
+                raise ValueError(f"expected [B,{C1 * rep},{R},{R}], got {(1, C1 * rep, h, wd)}")
+            geom.append([off, h, wd, ids.setdefault((h, wd), len(ids))])
+            off += s.size
+        if off >= 2 ** 31:
+            raise ValueError("a NativeBatch holds less than 2 GiB of pixels")
+        taps = [(resize_taps(h, R), resize_taps(wd, R)) for h, wd in ids]
+        T = max(t[1].shape[1] for pair in taps for t in pair)
+        start = np.zeros((len(taps), 2, R), np.int32)
+        w = np.zeros((len(taps), 2, R, T), np.float32)
+        for g, pair in enumerate(taps):
+            for ax, (st, wt) in enumerate(pair):
+                start[g, ax] = st
+                w[g, ax, :, :wt.shape[1]] = wt
+        pix = np.concatenate([np.ascontiguousarray(s).reshape(-1) for s in samples])
+        return cls(torch.from_numpy(pix), torch.tensor(geom, dtype=torch.int32), torch.from_numpy(start.reshape(-1)),
+                   torch.from_numpy(w), C1, rep, R, [(g[1], g[2]) for g in geom])
+
+    def __len__(self):
+        return self.geom.shape[0]
+
+    @property
+    def device(self):
+        return self.pix.device
+
+    @property
+    def is_cuda(self):
+        return self.pix.is_cuda
+
+    def _map(self, fn) -> "NativeBatch":
+        return NativeBatch(fn(self.pix), fn(self.geom), fn(self.start), fn(self.w), self.C1, self.rep, self.R, self.sizes)
+
+    def to(self, device, non_blocking: bool = False) -> "NativeBatch":
+        return self._map(lambda t: t.to(device, non_blocking=non_blocking))
+
+    def pin_memory(self) -> "NativeBatch":
+        return self._map(lambda t: t.pin_memory())
+
+    def supported(self) -> bool:
+        """Whether ffm_resize_u8 serves this batch (else it answers FFM_EUNSUP and the loader resizes on the host)."""
+        return self.R % 4 == 0 and self.T <= NATIVE_MAX_TAPS
 
 
 def _read_csv(path: str) -> Dict[str, list]:
@@ -97,9 +234,9 @@ class FairFedMedDataset:
         attrs = [int(raw[k]) for k in self.attributes] if (self.attribute_type is not None and self.attributes) else []
         return label, attrs
 
-    def raw(self, item):
+    def raw(self, item, native: bool = False):
         """(image in transport form [C1,H,W], channel repeat, label, attrs); uint8 when the file holds uint8 and no
-        resize is needed, else float32."""
+        resize is needed, else float32.  native=True: a uint8 sample is returned at its stored size, unresized."""
         with self._load(item) as raw:
             label, attrs = self._meta(raw)
             if self.modality_type == "slo_fundus":
@@ -109,6 +246,8 @@ class FairFedMedDataset:
                 img, rep = raw["oct_bscans"][::4], 1                   # 128 -> 32 B-scans (:639)
             else:                                                      # oct_bscans_3d: [1, D, H, W] volume
                 img, rep = raw["oct_bscans"][None], 1
+        if native and self.modality_type != "oct_bscans_3d" and img.dtype == np.uint8:
+            return np.ascontiguousarray(img), rep, label, attrs
         if self.modality_type != "oct_bscans_3d" and img.shape[1] != self.resolution:
             img = np.stack([resize_image(s.astype(np.float32), (self.resolution, self.resolution)) for s in img])
         if img.dtype != np.uint8:
@@ -157,10 +296,10 @@ class FedChexMimicDataset:
     def __len__(self):
         return len(self.data_files)
 
-    def raw(self, item):
+    def raw(self, item, native: bool = False):
         from PIL import Image
         img = np.array(Image.open(os.path.join(self.data_path, self.data_files[item])).convert("L"))[None, :, :]
-        if img.shape[1] != self.resolution:
+        if img.shape[1] != self.resolution and not (native and img.dtype == np.uint8):
             img = np.stack([resize_image(s.astype(np.float32), (self.resolution, self.resolution)) for s in img])
         attrs = [a[item] for a in self.data_attributes]
         return np.ascontiguousarray(img), (self.depth if self.depth > 1 else 1), self.disease_labels[item], attrs
@@ -183,12 +322,15 @@ class FedLoader:
     training, sequential for testing, batches in the dict contract {"img", "label", "attrs"}.
 
     transport="uint8" ships the sample's transport form when it is uint8 (``img`` is then uint8 [B,C1,H,W] and the
-    engine expands / repeats the channels on the GPU); "float32" ships what the reference ships.  Batches are
+    engine expands / repeats the channels on the GPU); "float32" ships what the reference ships; "native" ships the
+    stored uint8 samples at their stored sizes as a ``NativeBatch`` (``img`` has len() = B and .to() / .pin_memory(), no
+    shape) and the engine resizes them on the GPU - a batch with a sample that is not uint8, or one ffm_resize_u8 does not
+    serve, is resized on the host and shipped as float32; the 3D volumes are never resized and go as uint8.  Batches are
     assembled in pinned memory so that the trainer's ``.to(device, non_blocking=True)`` is an asynchronous copy."""
 
     def __init__(self, dataset, batch_size: int, train: bool, seed: int = 0, transport: str = "float32",
                  pin_memory: Optional[bool] = None):
-        assert transport in ("float32", "uint8")
+        assert transport in ("float32", "uint8", "native")
         self.dataset, self.batch_size, self.train, self.transport = dataset, batch_size, train, transport
         self.drop_last = train and len(dataset) >= batch_size
         self.gen = np.random.default_rng(seed)
@@ -200,18 +342,25 @@ class FedLoader:
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def _collate(self, idx: Sequence[int]) -> Dict[str, torch.Tensor]:
-        imgs, labels, attrs = [], [], []
-        for i in idx:
-            img, rep, label, a = self.dataset.raw(int(i))
-            if self.transport == "float32" or img.dtype != np.uint8:
-                img = img.astype(np.float32)
-                if rep > 1:
-                    img = np.repeat(img, rep, axis=0)
-            imgs.append(img)
-            labels.append(label)
-            attrs.append(a)
-        out = {"img": torch.from_numpy(np.stack(imgs)), "label": torch.tensor(labels, dtype=torch.int64),
-               "attrs": torch.tensor(attrs, dtype=torch.int64).reshape(len(idx), -1)}
+        native = self.transport == "native" and getattr(self.dataset, "modality_type", None) != "oct_bscans_3d"
+        samples = [self.dataset.raw(int(i), native=True) if native else self.dataset.raw(int(i)) for i in idx]
+        img = None
+        if native and all(s[0].dtype == np.uint8 for s in samples):
+            nb = NativeBatch.from_planes([s[0] for s in samples], samples[0][1], self.dataset.resolution)
+            img = nb if nb.supported() else None
+        if native and img is None:                                     # this batch takes the host resize
+            samples = [self.dataset.raw(int(i)) for i in idx]
+        if img is None:
+            imgs = []
+            for im, rep, _, _ in samples:
+                if self.transport == "float32" or native or im.dtype != np.uint8:
+                    im = im.astype(np.float32)
+                    if rep > 1:
+                        im = np.repeat(im, rep, axis=0)
+                imgs.append(im)
+            img = torch.from_numpy(np.stack(imgs))
+        out = {"img": img, "label": torch.tensor([s[2] for s in samples], dtype=torch.int64),
+               "attrs": torch.tensor([s[3] for s in samples], dtype=torch.int64).reshape(len(idx), -1)}
         if self.pin:
             out = {k: v.pin_memory() for k, v in out.items()}
         return out
@@ -251,8 +400,10 @@ class FedData:
 # ------------------------------------------------------------------------------------------------ synthetic files --
 def write_synthetic_fairfedmed(root: str, sites: int = 2, n_train: int = 12, n_test: int = 6, size: int = 224,
                                seed: int = 0, modality: str = "slo_fundus", attribute_type: str = "race",
-                               unknown_every: int = 0) -> str:
-    """A FairFedMed tree of random uint8 samples (tests, input-path benchmark).  Returns <root>/fairfedmed."""
+                               unknown_every: int = 0, sizes: Optional[Sequence] = None) -> str:
+    """A FairFedMed tree of random uint8 samples (tests, input-path benchmark).  Returns <root>/fairfedmed.
+    sizes: stored sizes taken in turn, sample k gets sizes[k % len(sizes)], each an int or a pair (rows, columns) of the stored
+    array; None writes every sample size x size."""
     g = np.random.Generator(np.random.Philox(key=[0xDA7A, seed & 0xFFFFFFFF]))
     base = os.path.join(root, DATASET_DIRS["FairFedMed"])
     os.makedirs(os.path.join(base, "all"), exist_ok=True)
@@ -267,11 +418,13 @@ def write_synthetic_fairfedmed(root: str, sites: int = 2, n_train: int = 12, n_t
                         "language": np.array(int(g.integers(0, 3)))}
                 if unknown_every and k % unknown_every == unknown_every - 1:
                     arrs[attribute_type] = np.array(-1)
+                hw = sizes[k % len(sizes)] if sizes else size
+                hw = (hw, hw) if np.isscalar(hw) else tuple(hw)
                 if modality == "slo_fundus":
-                    arrs["slo_fundus"] = g.integers(0, 256, size=(size, size), dtype=np.uint8)
+                    arrs["slo_fundus"] = g.integers(0, 256, size=hw, dtype=np.uint8)
                     arrs["oct_bscans"] = np.zeros((0,), np.uint8)
                 else:
-                    arrs["oct_bscans"] = g.integers(0, 256, size=(128, size, size), dtype=np.uint8)
+                    arrs["oct_bscans"] = g.integers(0, 256, size=(128,) + hw, dtype=np.uint8)
                     arrs["slo_fundus"] = np.zeros((0,), np.uint8)
                 np.savez(os.path.join(base, "all", name), **arrs)
                 names.append(name)

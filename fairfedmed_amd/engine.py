@@ -30,6 +30,7 @@ from . import _lib as L
 from ._lib import is16 as _is16
 from . import ops
 from .config import ModelCfg
+from .data import NativeBatch
 from .synth import manifest, trainable_keys
 
 Tensor = torch.Tensor
@@ -1100,18 +1101,29 @@ class FairLoRAEngine:
     # ------------------------------------------------------------- vision --
     def _as_f32(self, image: Tensor, slot: str = "_u8_stage") -> Tensor:
         """uint8 transport (fairfedmed_amd.data, transport="uint8"): expand on the GPU to the float32 batch the
-        reference's loader ships - a single SLO / X-ray channel is repeated to 3 (utils/data_utils.py:676-679)."""
-        if image.dtype != torch.uint8:
+        reference's loader ships - a single SLO / X-ray channel is repeated to 3 (utils/data_utils.py:676-679).  A
+        NativeBatch (transport="native") carries stored sizes and its own channel repeat: resized into the same buffer."""
+        native = isinstance(image, NativeBatch)       # transport="native": stored sizes, resized here (ffm_resize_u8)
+        if not native and image.dtype != torch.uint8:
             return image
-        if not image.is_cuda or image.dim() != 4:
-            raise TypeError("uint8 images must be CUDA tensors [B, C, H, W]")
-        b, c1 = image.shape[:2]
-        rep = 1 if self.cfg.dim_per_3d_slice else (3 // c1 if c1 in (1, 3) else 1)
+        if native:
+            if not image.is_cuda:
+                raise TypeError("a NativeBatch must be on the GPU (.to(device))")
+            if image.R != self.cfg.vision.image_size:
+                raise ValueError(f"the NativeBatch resizes to {image.R}, the tower takes {self.cfg.vision.image_size}")
+            b, shape = len(image), (len(image), image.C1 * image.rep, image.R, image.R)
+        else:
+            if not image.is_cuda or image.dim() != 4:
+                raise TypeError("uint8 images must be CUDA tensors [B, C, H, W]")
+            b, c1 = image.shape[:2]
+            rep = 1 if self.cfg.dim_per_3d_slice else (3 // c1 if c1 in (1, 3) else 1)
+            shape = (b, c1 * rep) + tuple(image.shape[2:])
         stage = getattr(self, slot, None)             # (the evaluation pass stages in a buffer of its own)
-        shape = (b, c1 * rep) + tuple(image.shape[2:])
         if stage is None or stage.shape[0] < b or tuple(stage.shape[1:]) != shape[1:]:
             stage = torch.empty(shape, device=self.device, dtype=torch.float32)
             setattr(self, slot, stage)
+        if native:
+            return ops.resize_u8(image, stage[:b])
         return ops.expand_u8(image.contiguous(), stage[:b], rep)
 
     def _check_batch(self, image: Tensor, limit: Optional[int] = None, what: str = "max_images") -> Tuple[int, int]:

@@ -96,7 +96,7 @@ def build_parser() -> argparse.ArgumentParser:
     a("--state-dict", type=str, default="", help="CustomCLIP state_dict (.pt) with the pretrained CLIP weights")
     a("--synthetic", action="store_true", help="synthetic batches instead of the dataset under --root")
     a("--synthetic-batches", type=int, default=4)
-    a("--transport", type=str, default="uint8", choices=["uint8", "float32"])
+    a("--transport", type=str, default="uint8", choices=["uint8", "float32", "native"])
     a("--input_size", type=int, default=0, help="INPUT.SIZE = (N, N); 0 keeps the configuration's (224)")
     a("--interpolate_pos", action="store_true",
       help="INPUT.INTERPOLATE_POS: run a ViT at an INPUT.SIZE other than its checkpoint's (a multiple of the patch size) with "

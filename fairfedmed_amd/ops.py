@@ -549,6 +549,23 @@ def expand_u8(src: Tensor, dst: Tensor, rep: int) -> Tensor:
     return dst
 
 
+def resize_u8(batch, dst: Tensor) -> Tensor:
+    """data.NativeBatch (stored uint8 samples of any size, on the device) -> fp32 [B, C1*rep, R, R]: the datasets' resize, the
+    float conversion and the channel repeat in one launch (ffm_resize_u8).  A batch the kernel does not serve raises."""
+    _dev(batch.pix, batch.geom, batch.start, batch.w, dst)
+    B, R = len(batch), batch.R
+    assert batch.pix.dtype == torch.uint8 and batch.geom.dtype == torch.int32 and batch.start.dtype == torch.int32
+    assert batch.w.dtype == torch.float32 and dst.dtype == torch.float32 and dst.is_contiguous()
+    assert all(t.is_contiguous() for t in (batch.pix, batch.geom, batch.start, batch.w))
+    assert tuple(batch.geom.shape) == (B, 4) and tuple(dst.shape) == (B, batch.C1 * batch.rep, R, R)
+    assert len(batch.sizes) == B and sum(batch.C1 * h * w for h, w in batch.sizes) == batch.pix.numel()
+    NG = batch.w.shape[0]
+    assert tuple(batch.w.shape) == (NG, 2, R, batch.T) and batch.start.numel() == NG * 2 * R
+    _call("ffm_resize_u8", L.ptr(batch.pix), L.ptr(batch.geom), L.ptr(batch.start), L.ptr(batch.w), L.ptr(dst), B, batch.C1,
+          batch.rep, R, batch.T, L.stream_ptr())
+    return dst
+
+
 EVAL_SLOTS = 10
 
 

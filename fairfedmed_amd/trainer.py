@@ -233,7 +233,8 @@ class GLP_OT_SVLoRA:
         if mcfg.dim_per_3d_slice:
             # every sample becomes C / DIM_PER_3D_SLICE ViT images; the volume depth comes from the data
             first = next(iter(self.fed_train_loader_x_dict[min(self.fed_train_loader_x_dict)]))
-            bs *= first["img"].shape[1] // mcfg.dim_per_3d_slice
+            img = first["img"]                        # (a data.NativeBatch has no shape: C1 planes, each repeated rep times)
+            bs *= (img.shape[1] if hasattr(img, "shape") else img.C1 * img.rep) // mcfg.dim_per_3d_slice
         self.model = CustomCLIP(mcfg, sd, dtype=dtype, max_images=bs, device=str(self.device))
         self.engine = self.model.engine
         # the per-step summary's evaluator counts ride inside the step, beside the backward pass (binary tasks, device

@@ -52,7 +52,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* ---- epilogue flags for ffm_gemm_nt ------------------------------------ */
@@ -580,6 +580,27 @@ int ffm_text_ctx_grad(const float* g, float* dctx, int n_prompts, int n_cls, int
  * result is what the reference's loader would have shipped as float32, bit for bit.
  */
 int ffm_expand_u8(const uint8_t* src, float* dst, int B, int C1, int HW, int rep, void* stream);
+
+/*
+ * Native-size uint8 transport: the loader ships every sample's stored pixels at the stored size and this call is the
+ * skimage.transform.resize(img, (R, R)) of the dataset classes (utils/data_utils.py:640-646, 662-667: order 1, mode
+ * 'reflect', anti-aliasing Gaussian when an axis shrinks, clip to the input range) plus the float conversion and the
+ * channel repeat of ffm_expand_u8, behind the H2D copy.
+ *   pix        u8, all planes of all images back to back (any alignment); image b is [C1, H_b, W_b]
+ *   geom       int32 [B][4] = {byte offset of the image in pix, H_b, W_b, table id}
+ *   tab_start  int32 [NG][2][R]: first source index of every output row (axis 0, over H) / column (axis 1, over W)
+ *   tab_w      fp32 [NG][2][R][T]: the T tap weights from that index on, zero-padded; a source index past the axis is
+ *              clamped to its last sample (its weight is zero)
+ *   dst        fp32 [B, C1*rep, R, R], 16-byte aligned; output channel c is plane c / rep
+ * Per plane: the vertical taps in ascending order, then the horizontal taps in ascending order, in fp32; the result
+ * clipped to the plane's own minimum and maximum.  One thread sums one output element in that fixed order (no atomics),
+ * so an image's bits depend neither on its neighbours in the batch nor on T's padding; a plane with H == W == R (tables of
+ * one tap of weight 1) comes out as ffm_expand_u8 leaves it, bit for bit.  One launch; any H, W >= 1.
+ * FFM_EUNSUP (nothing launched): R % 4 != 0, T > FFM_RESIZE_MAX_TAPS, B * C1 > 2^27.
+ */
+#define FFM_RESIZE_MAX_TAPS 32
+int ffm_resize_u8(const uint8_t* pix, const int32_t* geom, const int32_t* tab_start, const float* tab_w, float* dst,
+                  int B, int C1, int rep, int R, int T, void* stream);
 
 /*
  * Evaluator counts for binary tasks (evaluation/evaluator_oph.py:37-150; evaluation/metrics.py:197-311, 513-552;
