@@ -68,6 +68,7 @@ OPTIM_KINDS = {"sgd": 0, "adam": 1, "adamw": 2, "amsgrad": 3, "rmsprop": 4, "rad
 # name -> argtypes (restype is always int, except the two helpers)
 SIGNATURES = {
     "ffm_abi_version": [],
+    "ffm_switch": [_vp, C.POINTER(_i32)],
     "ffm_gemm_nt": [C.POINTER(GemmArgs), _i32, _vp],
     "ffm_gemm_splitk_floats": [_i32, _i32, _i32, _i32],
     "ffm_gemm_tiles_m": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],

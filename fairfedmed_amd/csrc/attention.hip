@@ -14,7 +14,7 @@
 //   backward: dQ kernel (same shape as forward); delta = rowsum(dO * O) is formed inside both kernels;
 //             dK/dV kernel: waves own 16-key tiles and sweep all queries.
 #include "common.h"
-#include <cstdlib>
+#include "switches.h"
 #include <type_traits>
 
 namespace {
@@ -495,15 +495,6 @@ template <typename T> int lds_dkv(int NFP) {
     return 2 * HD * tstride<T>(NFP * 16) * AT<T>::ES + 2 * NFP * 16 * 4 + (kStaged<T>() ? 2 * NFP * 16 * AT<T>::ROWB : 0);
 }
 
-template <typename F> int set_lds(F fn, int bytes) {
-    if (bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
 // ---------------------------------------------------------------------------
 // Second-generation kernels for the vision tower (bf16, no mask, 8..14 key fragments: L = 113..224 tokens).
 //
@@ -732,15 +723,12 @@ __global__ __launch_bounds__(a2_nw<P>() * 64) __attribute__((amdgpu_waves_per_eu
 }
 
 // FFM_ATTN_PARTS=4 (A/B runs): quarter heads of 4 waves instead of half heads of 7
-inline int attn_parts() {
-    static const int p = (getenv("FFM_ATTN_PARTS") && getenv("FFM_ATTN_PARTS")[0] == '4') ? 4 : 2;
-    return p;
-}
+inline int attn_parts() { return ffm_sw().attn_parts; }
 
 template <int NF, bool SH, int P>
 int run_fwd2p(const void* qkv, void* out, float* lse, int B, int L, int heads, hipStream_t s) {
     constexpr int lds = 2 * (SH ? NF * 16 - 8 : NF * 16) * 128;
-    int e = set_lds(attn2_fwd_kernel<NF, SH, P>, lds);
+    int e = ffm_set_max_lds(attn2_fwd_kernel<NF, SH, P>, lds);
     if (e) return e;
     const int BH = B * heads;
     hipLaunchKernelGGL((attn2_fwd_kernel<NF, SH, P>), dim3(((BH + 7) / 8) * 8 * P), dim3(a2_nw<P>() * 64), lds, s, (const bf16_t*)qkv,
@@ -983,9 +971,9 @@ int run_bwd2p(const void* qkv, const void* out, const void* dout, const float* l
     constexpr int R8 = SH ? NF * 16 - 8 : NF * 16;
     constexpr int lds_dq2 = 2 * NF * 16 * 128, lds_dkv2 = 2 * R8 * 128 + 2 * NF * 16 * 4;
     const int BH = B * heads;
-    int e = set_lds(attn2_bwd_dq_kernel<NF, false, P>, lds_dq2);
+    int e = ffm_set_max_lds(attn2_bwd_dq_kernel<NF, false, P>, lds_dq2);
     if (e) return e;
-    e = set_lds(attn2_bwd_dkv_kernel<NF, SH, P>, lds_dkv2);
+    e = ffm_set_max_lds(attn2_bwd_dkv_kernel<NF, SH, P>, lds_dkv2);
     if (e) return e;
     const dim3 grid(((BH + 7) / 8) * 8 * P), block(a2_nw<P>() * 64);
     hipLaunchKernelGGL((attn2_bwd_dq_kernel<NF, false, P>), grid, block, lds_dq2, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
@@ -1009,16 +997,6 @@ int run_bwd2(const void* qkv, const void* out, const void* dout, const float* ls
                             : run_bwd2s<NF, false>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
 }
 
-// FFM_ATTN=v1: always the first-generation kernels; FFM_ATTN=v2: the second generation where it applies (A/B runs).
-// Default: the third generation (attention3.hip: fat waves on 32x32x16 MFMAs) for 65..256 unmasked tokens in 16-bit storage.
-inline int attn_gen_forced() {
-    static const int g = (getenv("FFM_ATTN") && getenv("FFM_ATTN")[0] == 'v' && getenv("FFM_ATTN")[1] >= '1' && getenv("FFM_ATTN")[1] <= '3')
-                             ? getenv("FFM_ATTN")[1] - '0' : 0;
-    return g;
-}
-inline bool attn_v1_forced() { return attn_gen_forced() == 1; }
-inline bool attn3_allowed() { return attn_gen_forced() == 0 || attn_gen_forced() == 3; }
-
 inline int pick_split(int bh, int NF) {
     // aim for >= ~3 blocks per CU while keeping >= 4 tiles (one per wave) per block
     int s = 1;
@@ -1034,7 +1012,7 @@ int run_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int
         // enough (b, h) pairs to fill the chip: one wave per 16-query tile and no q-split, so K / V are staged once
         // per pair and no wave runs two tiles back to back
         constexpr int NTH = NFP <= 14 ? 64 * NFP : 512;
-        int e = set_lds(attn_fwd_kernel<T, NFP, NTH>, lds);
+        int e = ffm_set_max_lds(attn_fwd_kernel<T, NFP, NTH>, lds);
         if (e) return e;
         hipLaunchKernelGGL((attn_fwd_kernel<T, NFP, NTH>), dim3(B * heads, 1), dim3(NTH), lds, s, (const T*)qkv, (T*)out,
                            lse, L, heads, causal, 1);
@@ -1042,7 +1020,7 @@ int run_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int
         return FFM_OK;
     }
     const int split = pick_split(B * heads, NF);
-    int e = set_lds(attn_fwd_kernel<T, NFP, 256>, lds);
+    int e = ffm_set_max_lds(attn_fwd_kernel<T, NFP, 256>, lds);
     if (e) return e;
     hipLaunchKernelGGL((attn_fwd_kernel<T, NFP, 256>), dim3(B * heads, split), dim3(256), lds, s, (const T*)qkv, (T*)out,
                        lse, L, heads, causal, split);
@@ -1055,13 +1033,13 @@ int run_bwd(const void* qkv, const void* out, const void* dout, const float* lse
             int L, int heads, int causal, hipStream_t s) {
     (void)delta;          // kept in the ABI as scratch; the row sums of dO * O are formed inside the two kernels
     int lds = lds_dq<T>(NFP);
-    int e = set_lds(attn_bwd_dq_kernel<T, NFP, kStaged<T>(), kBwThreads<T, NFP>()>, lds);
+    int e = ffm_set_max_lds(attn_bwd_dq_kernel<T, NFP, kStaged<T>(), kBwThreads<T, NFP>()>, lds);
     if (e) return e;
     hipLaunchKernelGGL((attn_bwd_dq_kernel<T, NFP, kStaged<T>(), kBwThreads<T, NFP>()>), dim3(B * heads), dim3(kBwThreads<T, NFP>()), lds, s,
                        (const T*)qkv, (const T*)dout, lse, (const T*)out, (T*)dqkv, L, heads, causal);
     FFM_CHECK_LAUNCH();
     lds = lds_dkv<T>(NFP);
-    e = set_lds(attn_bwd_dkv_kernel<T, NFP, kStaged<T>(), kBwThreads<T, NFP>()>, lds);
+    e = ffm_set_max_lds(attn_bwd_dkv_kernel<T, NFP, kStaged<T>(), kBwThreads<T, NFP>()>, lds);
     if (e) return e;
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, NFP, kStaged<T>(), kBwThreads<T, NFP>()>), dim3(B * heads), dim3(kBwThreads<T, NFP>()), lds, s,
                        (const T*)qkv, (const T*)dout, lse, (const T*)out, (T*)dqkv, L, heads, causal);
@@ -1081,6 +1059,17 @@ int run_bwd(const void* qkv, const void* out, const void* dout, const float* lse
         case 16: return CALL(16);        \
         default: return FFM_EUNSUP;      \
     }
+// the second generation's shapes: 9..14 key fragments
+#define NF2_SWITCH(CALL)                 \
+    switch ((L + 15) / 16) {             \
+        case 9: return CALL(9);          \
+        case 10: return CALL(10);        \
+        case 11: return CALL(11);        \
+        case 12: return CALL(12);        \
+        case 13: return CALL(13);        \
+        case 14: return CALL(14);        \
+        default: return FFM_EUNSUP;      \
+    }
 
 template <typename T>
 int dispatch_fwd(int nfp, const void* qkv, void* out, float* lse, int B, int L, int heads, int causal, hipStream_t s) {
@@ -1096,9 +1085,23 @@ int dispatch_bwd(int nfp, const void* qkv, const void* out, const void* dout, co
 #undef CALL
 }
 
+// the vision tower's shapes: attn2_* (half a head per block)
+int dispatch_fwd2(const void* qkv, void* out, float* lse, int B, int L, int heads, hipStream_t s) {
+#define CALL(N) run_fwd2<N>(qkv, out, lse, B, L, heads, s)
+    NF2_SWITCH(CALL)
+#undef CALL
+}
+int dispatch_bwd2(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int L,
+                  int heads, hipStream_t s) {
+#define CALL(N) run_bwd2<N>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s)
+    NF2_SWITCH(CALL)
+#undef CALL
+}
+
 }  // namespace
 
 // attention3.hip
+bool ffm_attn3_serves(int L, int dtype);
 int ffm_attn3_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int dtype, hipStream_t s);
 int ffm_attn3_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int L, int heads,
                   int dtype, hipStream_t s, const float* ln_wg, const float* ln_d, float* ln_part);
@@ -1107,29 +1110,37 @@ int ffm_attn_long_fwd(const void* qkv, void* out, float* lse, int B, int L, int 
 int ffm_attn_long_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int L,
                       int heads, int causal, int dtype, hipStream_t s);
 
+// Which kernels serve a call; the four entry points below ask here and nowhere else.
+// FFM_ATTN=v1: always the first-generation kernels; FFM_ATTN=v2: the second generation where it applies (A/B runs).
+// Default (and v3): the third generation (attention3.hip: fat waves on 32x32x16 MFMAs) for 65..256 unmasked tokens in 16-bit
+// storage.  More than 256 tokens: the streaming kernels, whatever the switch says (they validate the dtype themselves).
+// `dtype` is the caller's real code and goes on to the other two files as it is; FFM_BF16 is THIS object's 16-bit type
+// (common.h), so in the IEEE-half twin the second and first generation serve half.
+enum attn_gen { ATTN_NONE, ATTN_FIRST, ATTN_SECOND, ATTN_THIRD, ATTN_LONG };
+static attn_gen attn_route(int L, int causal, int dtype) {
+    if (L > 256) return ATTN_LONG;
+    const int gen = ffm_sw().attn_gen, nf = (L + 15) / 16;
+    if (!causal && (gen == 0 || gen == 3) && ffm_attn3_serves(L, dtype)) return ATTN_THIRD;
+    if (dtype == FFM_BF16 && !causal && gen != 1 && nf >= 9 && nf <= 14) return ATTN_SECOND;
+    if (dtype == FFM_BF16 || dtype == FFM_F32) return ATTN_FIRST;
+    return ATTN_NONE;
+}
+
 extern "C" int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int causal,
                                  int dtype, void* stream) {
     if (!qkv || !out || B <= 0 || L <= 0 || heads <= 0) return FFM_EINVAL;
     if (((uintptr_t)qkv | (uintptr_t)out) & 15) return FFM_EINVAL;
-    if (L > 256) return ffm_attn_long_fwd(qkv, out, lse, B, L, heads, causal, dtype, (hipStream_t)stream);
     const int nfp = (((L + 15) / 16) + 1) & ~1;
     hipStream_t s = (hipStream_t)stream;
-    if ((dtype == FFM_BF16 || dtype == FFM_F16) && !causal && attn3_allowed()) {
-        const int e = ffm_attn3_fwd(qkv, out, lse, B, L, heads, dtype, s);
-        if (e != FFM_EUNSUP) return e;
+    switch (attn_route(L, causal, dtype)) {
+        case ATTN_LONG: return ffm_attn_long_fwd(qkv, out, lse, B, L, heads, causal, dtype, s);
+        case ATTN_THIRD: return ffm_attn3_fwd(qkv, out, lse, B, L, heads, dtype, s);
+        case ATTN_SECOND: return dispatch_fwd2(qkv, out, lse, B, L, heads, s);
+        case ATTN_FIRST:
+            if (dtype == FFM_BF16) return dispatch_fwd<bf16_t>(nfp, qkv, out, lse, B, L, heads, causal, s);
+            return dispatch_fwd<float>(nfp, qkv, out, lse, B, L, heads, causal, s);
+        case ATTN_NONE: break;
     }
-    if (dtype == FFM_BF16 && !causal && !attn_v1_forced()) {
-        switch ((L + 15) / 16) {                        // the vision tower's shapes: attn2_* (half a head per block)
-            case 9: return run_fwd2<9>(qkv, out, lse, B, L, heads, s);
-            case 10: return run_fwd2<10>(qkv, out, lse, B, L, heads, s);
-            case 11: return run_fwd2<11>(qkv, out, lse, B, L, heads, s);
-            case 12: return run_fwd2<12>(qkv, out, lse, B, L, heads, s);
-            case 13: return run_fwd2<13>(qkv, out, lse, B, L, heads, s);
-            case 14: return run_fwd2<14>(qkv, out, lse, B, L, heads, s);
-        }
-    }
-    if (dtype == FFM_BF16) return dispatch_fwd<bf16_t>(nfp, qkv, out, lse, B, L, heads, causal, s);
-    if (dtype == FFM_F32) return dispatch_fwd<float>(nfp, qkv, out, lse, B, L, heads, causal, s);
     return FFM_EINVAL;
 }
 
@@ -1137,25 +1148,17 @@ extern "C" int ffm_attention_bwd(const void* qkv, const void* out, const void* d
                                  void* dqkv, int B, int L, int heads, int causal, int dtype, void* stream) {
     if (!qkv || !out || !dout || !lse || !delta || !dqkv || B <= 0 || L <= 0 || heads <= 0) return FFM_EINVAL;
     if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) & 15) return FFM_EINVAL;
-    if (L > 256) return ffm_attn_long_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, dtype, (hipStream_t)stream);
     const int nfp = (((L + 15) / 16) + 1) & ~1;
     hipStream_t s = (hipStream_t)stream;
-    if ((dtype == FFM_BF16 || dtype == FFM_F16) && !causal && attn3_allowed()) {
-        const int e = ffm_attn3_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, dtype, s, nullptr, nullptr, nullptr);
-        if (e != FFM_EUNSUP) return e;
+    switch (attn_route(L, causal, dtype)) {
+        case ATTN_LONG: return ffm_attn_long_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, dtype, s);
+        case ATTN_THIRD: return ffm_attn3_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, dtype, s, nullptr, nullptr, nullptr);
+        case ATTN_SECOND: return dispatch_bwd2(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
+        case ATTN_FIRST:
+            if (dtype == FFM_BF16) return dispatch_bwd<bf16_t>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
+            return dispatch_bwd<float>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
+        case ATTN_NONE: break;
     }
-    if (dtype == FFM_BF16 && !causal && !attn_v1_forced()) {
-        switch ((L + 15) / 16) {
-            case 9: return run_bwd2<9>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
-            case 10: return run_bwd2<10>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
-            case 11: return run_bwd2<11>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
-            case 12: return run_bwd2<12>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
-            case 13: return run_bwd2<13>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
-            case 14: return run_bwd2<14>(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
-        }
-    }
-    if (dtype == FFM_BF16) return dispatch_bwd<bf16_t>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
-    if (dtype == FFM_F32) return dispatch_bwd<float>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
     return FFM_EINVAL;
 }
 
@@ -1166,7 +1169,7 @@ extern "C" int ffm_attention_bwd(const void* qkv, const void* out, const void* d
 // (ffm_attention_bwd_lnstat_ok says so beforehand).
 extern "C" int ffm_attention_bwd_lnstat_ok(int L, int causal, int dtype) {
     // (97..256 tokens: the dK/dV kernel lays its four 64-float tables over the row constants of at least four 32-token tiles)
-    return ((dtype == FFM_BF16 || dtype == FFM_F16) && !causal && attn3_allowed() && L > 96 && L <= 256) ? 1 : 0;
+    return (attn_route(L, causal, dtype) == ATTN_THIRD && L > 96) ? 1 : 0;
 }
 
 extern "C" int ffm_attention_bwd_lnstat(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

@@ -29,7 +29,7 @@
 //
 // Replaces nn.MultiheadAttention's core (clip/model.py:350-352) and its autograd on the vision tower.
 #include "common.h"
-#include <cstdlib>
+#include "switches.h"
 #include <type_traits>
 
 namespace {
@@ -812,23 +812,12 @@ void attn3_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ d_o, 
     A3_RSTAMP(15);
 }
 
-inline int a3_map() {
-    static const int m = (getenv("FFM_ATTN3_MAP") && getenv("FFM_ATTN3_MAP")[0] == '0') ? 0 : 1;
-    return m;
-}
-
-template <typename F> int set_lds3(F fn, int bytes) {
-    if (bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
+inline int a3_map() { return ffm_sw().attn3_map; }
 
 template <typename T, int NT>
 int run_fwd3(const void* qkv, void* out, float* lse, int B, int L, int heads, hipStream_t s) {
     const int R8 = (L + 7) & ~7, lds = 2 * R8 * 128, BH = B * heads;
-    int e = set_lds3(attn3_fwd_kernel<T, NT>, lds);
+    int e = ffm_set_max_lds(attn3_fwd_kernel<T, NT>, lds);
     if (e) return e;
     hipLaunchKernelGGL((attn3_fwd_kernel<T, NT>), dim3(((BH + 7) / 8) * 16), dim3(64 * Geo<NT>::NW), lds, s, (const T*)qkv, (T*)out, lse, L,
                        heads, BH, a3_map());
@@ -841,9 +830,9 @@ int run_bwd3(const void* qkv, const void* out, const void* dout, const float* ls
     // (+ 512 B in the dQ kernel: the LayerNorm-backward tables of the head - 51 712 B is still 41 of the 1280-byte LDS units,
     // three blocks per CU; the dK/dV kernel lays its 1 KB over the row constants at its end, see there)
     const int R8 = (L + 7) & ~7, lds_dq = 2 * R8 * 128 + 512, lds_dkv = 2 * R8 * 128 + 2 * 32 * NT * 4, BH = B * heads;
-    int e = set_lds3(attn3_bwd_dq_kernel<T, NT>, lds_dq);
+    int e = ffm_set_max_lds(attn3_bwd_dq_kernel<T, NT>, lds_dq);
     if (e) return e;
-    e = set_lds3(attn3_bwd_dkv_kernel<T, NT>, lds_dkv);
+    e = ffm_set_max_lds(attn3_bwd_dkv_kernel<T, NT>, lds_dkv);
     if (e) return e;
     const dim3 grid(((BH + 7) / 8) * 16), block(64 * Geo<NT>::NW);
     // (the dK/dV kernel on a second stream BESIDE the dQ kernel - a timing probe with a stale delta, to price ONE launch
@@ -867,6 +856,12 @@ extern "C" int ffm_attn3_read_stamps(unsigned long long* host, int n) {
 #endif
 
 // Entry points for attention.hip's dispatcher (same library, not part of the C ABI): FFM_EUNSUP = not this kernel's shape.
+// ffm_attn3_serves says beforehand which shapes those are: 65..256 tokens (3..8 tiles of 32) in 16-bit storage; `dtype` is
+// the caller's real code here as in the two launchers (this file is compiled once and serves the IEEE-half twin too)
+bool ffm_attn3_serves(int L, int dtype) {
+    const int nt = (L + 31) / 32;
+    return L > 64 && L <= 256 && (dtype == FFM_BF16 || dtype == FFM_F16) && nt >= 3 && nt <= 8;
+}
 int ffm_attn3_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int dtype, hipStream_t s) {
     if (L <= 64 || L > 256) return FFM_EUNSUP;
 #define FWD3(T)                                                          \

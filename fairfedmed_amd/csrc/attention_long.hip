@@ -482,14 +482,6 @@ template <typename T> constexpr int lds_fwd() { return rm_bytes<T>() + tr_bytes<
 template <typename T> constexpr int lds_dq() { return tr_bytes<T>() + 2 * rm_bytes<T>(); }
 template <typename T> constexpr int lds_dkv() { return 2 * tr_bytes<T>() + 2 * rm_bytes<T>() + 2 * KT * 4; }
 
-template <typename F> int set_lds(F fn, int bytes) {
-    if (bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
 // one block per (b, h, tile): FFM_EUNSUP when the grid's thread count does not fit 32 bits (HIP's limit per dimension)
 inline bool grid_of(int B, int L, int heads, unsigned& blocks) {
     const long long n = (long long)B * heads * ((L + KT - 1) / KT);
@@ -510,7 +502,7 @@ int run_bwd(const void* qkv, const void* out, const void* dout, const float* lse
             int causal, hipStream_t s) {
     unsigned blocks;
     if (!grid_of(B, L, heads, blocks)) return FFM_EUNSUP;
-    const int e = set_lds(al_bwd_dkv_kernel<T>, lds_dkv<T>());    // fp32: 68 096 B
+    const int e = ffm_set_max_lds(al_bwd_dkv_kernel<T>, lds_dkv<T>());    // fp32: 68 096 B
     if (e) return e;
     hipLaunchKernelGGL((al_bwd_dq_kernel<T>), dim3(blocks), dim3(NTH), lds_dq<T>(), s, (const T*)qkv, (const T*)dout, lse, (const T*)out,
                        (T*)dqkv, delta, L, heads, causal);

@@ -39,6 +39,15 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
         if (e__ != hipSuccess) return (int)e__;              \
     } while (0)
 
+// A launch with more than 64 KB of dynamic LDS has to raise the kernel's limit first (a hipError_t, 0 = fine).
+template <typename F> int ffm_set_max_lds(F fn, int bytes) {
+    if (bytes > 65536) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Element traits: T is float or bf16_t.  A "chunk" is 16 bytes of a row.
 // ---------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 //   AvgPool2d(2), residual add + ReLU, attention-pool token assembly (mean token + positional embedding)
 // All of it is HBM-bound elementwise / reduction work; 16-byte accesses along C.
 #include "common.h"
-#include <cstdlib>
+#include "switches.h"
 
 namespace {
 
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 constexpr int BNF_STRIP_BYTES = 128;
 struct bn_fold { bool on; int G, strip; };
 inline bn_fold bn_fold_geom(int rows, int C, int vn, int given_part_rows) {
-    static const int max_rows = getenv("FFM_BN_FOLD_ROWS") ? atoi(getenv("FFM_BN_FOLD_ROWS")) : 32768;
+    const int max_rows = ffm_sw().bn_fold_rows;
     bn_fold f{false, 0, BNF_STRIP_BYTES / 16};
     if (rows > max_rows) return f;
     int G = 1;
@@ -701,7 +701,7 @@ namespace {
 // grid of the apply kernels: blockIdx.y = group of 256 channel chunks, blockIdx.x walks the rows; FFM_BN_RPT rows per
 // thread (default 2; 1 / 2 / 4 / 8 measured 7.09 / 7.04 / 7.05 / 7.24 ms on the RN50 step)
 inline dim3 bn_apply_grid(int rows, int C, int vn) {
-    static const int rpt = getenv("FFM_BN_RPT") ? atoi(getenv("FFM_BN_RPT")) : 2;
+    const int rpt = ffm_sw().bn_rpt;
     const int cc = C / vn, tpr = cc < 256 ? cc : 256, nrl = 256 / tpr, gy = (cc + 255) / 256;
     int gx = (rows + nrl * rpt - 1) / (nrl * rpt);
     const int cap = 65535;

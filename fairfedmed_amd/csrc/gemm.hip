@@ -10,7 +10,7 @@
 // to the per-lane SOURCE address (lane -> row r = l>>3, slot p = l&7 reads
 // global chunk p ^ (r&7)) and again on the ds_read side.
 #include "gemm_panel.h"
-#include <cstdlib>
+#include "switches.h"
 
 namespace {
 
@@ -987,7 +987,7 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
     }
     hipStream_t s = (hipStream_t)stream;
     if (ffm_skinny_ok(a, dtype) && !a.colstat_part) {                    // (column sums: the 128x128 kernel's epilogue)
-        static const bool off = getenv("FFM_SKINNY") && getenv("FFM_SKINNY")[0] == 'o';      // FFM_SKINNY=off: A/B runs
+        const bool off = ffm_sw().skinny_off;                                // FFM_SKINNY=off: A/B runs
         if (!off || dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) return ffm_skinny_launch(a, dtype, s);
     }
     if (dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) return FFM_EUNSUP;      // split-operand products: skinny shapes only
@@ -1014,7 +1014,7 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
     }
     // fewer tiles than CUs and a K loop worth pipelining (16-bit operands): the four-stage ring, one block per CU
     // (FFM_GEMM_DEEP=0: A/B runs)
-    static const bool deep_on = !(getenv("FFM_GEMM_DEEP") && getenv("FFM_GEMM_DEEP")[0] == '0');
+    const bool deep_on = ffm_sw().gemm_deep;
     const long tiles_ = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     const bool deep = deep_on && dtype == FFM_BF16 && tiles_ <= 256 && (size_t)a.K * es / KT_BYTES >= 6;
 #define FFM_GEMM_CASE(RKB, F)                                                                   \
@@ -1341,7 +1341,7 @@ int conv_ksplit_2buf(int M, int N, int Kp, size_t es, bool scratch, int64_t scra
 // keeps tiles x S <= 256 (layer3: 98 tiles, 3 -> 2 slices; layer4: 52 tiles, 6 -> 4) and the launch takes the deep ring.
 // deep (out): this launch runs the four-stage ring.  FFM_CONV_DEEP=0: the two-buffer plan (A/B runs).
 int conv_ksplit(int M, int N, int Kp, size_t es, bool scratch, int64_t scratch_elems, bool* deep = nullptr) {
-    static const bool deep_on = !(getenv("FFM_CONV_DEEP") && getenv("FFM_CONV_DEEP")[0] == '0');
+    const bool deep_on = ffm_sw().conv_deep;
     int S = conv_ksplit_2buf(M, N, Kp, es, scratch, scratch_elems);
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (int)((size_t)Kp * es / KT_BYTES);
     bool d = false;
@@ -1422,8 +1422,7 @@ static int conv3x3_impl(const void* x, const void* w, void* y, int B, int H, int
     // 56 x 56).  FFM_CONV_NARROW=off: the 128x128 kernel (A/B runs); FFM_CONV_NARROW=<t>: also N = 128 / 256 / ... as 64-wide
     // column tiles when the launch has fewer than t 128x128 tiles (measured at t = 512 / 1000 on RN50 bs 32: no gain)
     const int t128 = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    static const char* nenv = getenv("FFM_CONV_NARROW");
-    static const int narrow_max = nenv ? (nenv[0] == 'o' ? -1 : atoi(nenv)) : 0;
+    const int narrow_max = ffm_sw().conv_narrow_max;
     if (S == 1 && narrow_max >= 0 && (a.N == 32 || a.N == 64 || (a.N % 64 == 0 && t128 < narrow_max))) {
         if (bnb) {
             if (a.N == 32) return dtype == FFM_BF16 ? launch_conv_narrow<bf16_t, 32, true>(ka, s) : launch_conv_narrow<float, 32, true>(ka, s);

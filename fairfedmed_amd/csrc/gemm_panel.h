@@ -22,7 +22,7 @@ struct ffm_panel_cfg {
     int pw;          // waves per block
     int ks;          // 1: the 8 waves are 4 column slabs x 2 K halves (gemm_panel_impl.h, KS) - the tile is 64*nf wide
     bool built;      // false: measured, lost, not instantiated any more (the row stays: indices and mask bits do not move)
-    bool masked;     // selected only with bit <index> of FFM_PANEL_MASK set (gemm_panel.hip: FFM_PANEL_MASK_DEFAULT)
+    bool masked;     // selected only with bit <index> of FFM_PANEL_MASK set (switches.h: FFM_PANEL_MASK_DEFAULT)
     bool lgrad;      // has the FFM_EPI_LGRAD epilogues
     bool lnb_apply;  // has the FFM_EPI_LNB_APPLY epilogue
     int min_k;       // not selected for a shorter K (0: no limit of its own)

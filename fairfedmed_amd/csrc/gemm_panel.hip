@@ -2,9 +2,9 @@
 // (kernel: gemm_panel_impl.h; the FairLoRA rows: gemm_panel_rk*.hip)
 // What tiles and epilogues exist is written in gemm_panel.h alone: the selector below adds the conditions on run-time
 // arguments, the switches and the cost model; ffm_panel_launch instantiates the plain rows (`unit` 0 of the table).
-// Enabling a masked row by default is its bit in FFM_PANEL_MASK_DEFAULT.
+// Enabling a masked row by default is its bit in FFM_PANEL_MASK_DEFAULT (switches.h).
 #include "gemm_panel_impl.h"
-#include <cstdlib>
+#include "switches.h"
 
 // Default set of the newer configurations (tools/bench_panel.py, isolated launches at bs 32; FFM_PANEL_MASK=<int> for A/B):
 //   7  208x384 FairLoRA, two waves per SIMD: c_fc forward 53.8 -> 44.7 us, dX(c_proj) 50.5 -> 44.5 us
@@ -16,9 +16,6 @@
 // 36.1, dX(qkv) 25.0 -> 23.7, but IN THE STEP, beside the text tower and the LoRA-gradient reductions, the same launches
 // take what the 4-wave tiles take (44.0 / 43.8, 40.5 / 38.4 us) and the step is 0.03 ms slower: 4.73 -> 4.77 ms twice in
 // one call); tests/test_kernels_gpu.py runs the panel tests with it switched on and on the round-2 tiles alone.
-#ifndef FFM_PANEL_MASK_DEFAULT
-#define FFM_PANEL_MASK_DEFAULT ((1 << 7) | (1 << 8) | (1 << 10))
-#endif
 
 namespace {
 
@@ -50,17 +47,10 @@ int ffm_panel_select(int M, int N, int K, int flags, int rank, int dtype, bool p
     if (rk && (rank <= 0 || rank > 16 || ((flags & FFM_EPI_LNB_APPLY) && rank > 14) || ((flags & FFM_EPI_LGRAD) && rank % 4))) return -1;
     flags &= ~FFM_EPI_RANKOP;
     // FFM_PANEL=off: always the 128x128 kernel (A/B runs); read once per process, not per launch
-    static const bool panel_off = [] {
-        const char* f = getenv("FFM_PANEL");
-        return f && (f[0] == 'o' || f[0] == '0');
-    }();
-    if (panel_off) return -1;
+    if (ffm_sw().panel_off) return -1;
     // The rows marked `masked` in FFM_PANEL_CFGS are enabled by bit <index> of a mask (default FFM_PANEL_MASK_DEFAULT;
     // FFM_PANEL_MASK=<int> overrides, A/B runs)
-    static const int exp_mask = [] {
-        const char* f = getenv("FFM_PANEL_MASK");
-        return f ? atoi(f) : FFM_PANEL_MASK_DEFAULT;
-    }();
+    const int exp_mask = ffm_sw().panel_mask;
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     long best = ((t128 + 255) / 256) * 256;
     int pick = -1;

@@ -5,21 +5,12 @@
 // up to 8 K32 steps before the first MFMA, and the partial accumulators meet in LDS: N/16 = 32..128 blocks.
 // Operand types: see SkOps; epilogues: none, bias, bias+residual, bias+GELU, dGELU.
 #include "gemm_panel.h"
-#include <cstdlib>
+#include "switches.h"
 
-#ifndef FFM_SKINNY_CAP_DEFAULT
-#define FFM_SKINNY_CAP_DEFAULT 0
-#endif
 // Diagnostic twins only (tools/side_abl.sh): 1 = no weight loads, 2 = no activation loads (results are garbage) - which of
 // the text tower's two operand streams is it that slows the vision chain's kernels down?
 #ifndef FFM_SKINNY_ABL
 #define FFM_SKINNY_ABL 0
-#endif
-#ifndef FFM_SKINNY_NT_DEFAULT
-#define FFM_SKINNY_NT_DEFAULT 2
-#endif
-#ifndef FFM_SKINNY_MINB_DEFAULT
-#define FFM_SKINNY_MINB_DEFAULT 1
 #endif
 
 namespace {
@@ -441,8 +432,7 @@ __global__ __launch_bounds__(256) void skinny_splitk_finish_kernel(ffm_gemm_args
 // switches it off: A/B runs), K of at least FFM_SKINNY_SPLITK_MIN (default 4) slices of 128.  Measured on the bench step, three
 // alternating runs each in one call (profiles/r06_splitk_ab3.txt): off 4.669, N <= 512 only 4.677, all products 4.652 ms
 inline int sk_slices(int M, int N, int K) {
-    static const int nmax = getenv("FFM_SKINNY_SPLITK") ? atoi(getenv("FFM_SKINNY_SPLITK")) : 2048;
-    static const int smin = getenv("FFM_SKINNY_SPLITK_MIN") ? atoi(getenv("FFM_SKINNY_SPLITK_MIN")) : 4;
+    const int nmax = ffm_sw().skinny_splitk, smin = ffm_sw().skinny_splitk_min;
     if (M > 48 || N > nmax || N % 32 || K % SKS_K || K / SKS_K < smin || K / SKS_K > 64) return 0;
     return K / SKS_K;
 }
@@ -471,16 +461,14 @@ int launch_splitk(const ffm_gemm_args& a, hipStream_t s) {
 // waiting (the side streams cost the chain ~0.4 ms per step).  FFM_SKINNY_CAP=<n> caps the grid at n
 // blocks (0 = one block per tile).
 inline int sk_grid(int tiles) {
-    static const int cap = getenv("FFM_SKINNY_CAP") ? atoi(getenv("FFM_SKINNY_CAP")) : FFM_SKINNY_CAP_DEFAULT;
+    const int cap = ffm_sw().skinny_cap;
     return cap > 0 && tiles > cap ? cap : tiles;
 }
 
 // Tiles per block of the X3 product: FFM_SKINNY_NT = 1 | 2 | 4; a product whose N does not divide takes fewer.
 inline int sk_nt(int N) {
-    static const int want = getenv("FFM_SKINNY_NT") ? atoi(getenv("FFM_SKINNY_NT")) : FFM_SKINNY_NT_DEFAULT;
-    static const int minb = getenv("FFM_SKINNY_MINB") ? atoi(getenv("FFM_SKINNY_MINB")) : FFM_SKINNY_MINB_DEFAULT;
-    static const int want_n = getenv("FFM_SKINNY_NT_NARROW") ? atoi(getenv("FFM_SKINNY_NT_NARROW")) : want;   // N <= 512
-    const int w = N <= 512 ? want_n : want;
+    const int minb = ffm_sw().skinny_minb;
+    const int w = N <= 512 ? ffm_sw().skinny_nt_narrow : ffm_sw().skinny_nt;      // (the narrow one defaults to the other)
     int nt = w >= 4 ? 4 : (w >= 2 ? 2 : 1);
     while (nt > 1 && (N % (SK_COLS * nt) || N / (SK_COLS * nt) < minb)) nt >>= 1;     // never fewer than minb blocks
     return nt;

@@ -168,7 +168,8 @@ def _ds_rows(rows: int, N: int, K: int, rank: int, dtype, packed: Optional[bool]
 @dataclass(frozen=True)
 class Switches:
     """Every Python-side A/B switch of the engines, read from the environment ONCE, when an engine is constructed
-    (FairLoRAEngine.sw).  The kernel-side switches (getenv in csrc/) are the library's own."""
+    (FairLoRAEngine.sw).  The kernel-side switches are the library's own: the table of csrc/switches.h,
+    read once per process as well and readable through ops.switch (ffm_switch)."""
     red_at: Optional[int] = None           # FFM_RED_AT=0|1|2: where a block's LoRA-gradient reductions start (unset: by row count)
     lgrad: bool = True                     # FFM_LGRAD=0: the two large reductions as launches again, not inside dX(c_proj)
     pack_out: bool = True                  # FFM_PACK_OUT=0: patch embedding / final projection weights not in fragment order

@@ -102,6 +102,14 @@ class RankOp:
         self.lgrad = lgrad
 
 
+def switch(name: str) -> int:
+    """The value the library uses for the switch whose environment variable is `name` (ffm_switch; the table:
+    csrc/switches.h; booleans as 0 / 1).  Read-only: the table is read once per process."""
+    v = C.c_int32()
+    L.check(L.load().ffm_switch(name.encode(), C.byref(v)), f"ffm_switch({name})")
+    return v.value
+
+
 def gemm_tiles_m(M: int, N: int = 128, K: int = 128, flags: int = 0, rank: int = 0, dtype=torch.float32,
                  packed: bool = False) -> int:
     """Row tiles (= dS partial rows) of the kernel ffm_gemm_nt picks for this call."""

@@ -9,7 +9,10 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller (PyTorch's
- *     allocator); the library allocates nothing and keeps no global state;
+ *     allocator); the library allocates nothing, and its only process-wide
+ *     state is the switch table of csrc/switches.h: read from the environment
+ *     once, at the first call that needs a switch, read-only afterwards and
+ *     open to ffm_switch below;
  *   - `stream` is a hipStream_t passed as void*; calls only enqueue work;
  *   - `dtype` selects the activation / frozen-weight type: FFM_F32 or FFM_BF16.
  *     LoRA parameters, LayerNorm parameters, biases, statistics, logits and
@@ -54,6 +57,11 @@ extern "C" {
 /* library / build identification: returns FFM_ABI_VERSION */
 #define FFM_ABI_VERSION 14  /* still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
+
+/* The value in use for the diagnostic switch whose environment variable is `name` ("FFM_PANEL", "FFM_ATTN", ...: the rows
+ * of csrc/switches.h, listed in INTEGRATION.md); booleans as 0 / 1.  FFM_EINVAL for a name that is not in the table or a
+ * NULL argument (`*value` is then left alone).  There is no setter: the table is read once per process.  Needs no GPU. */
+int ffm_switch(const char* name, int* value);
 
 /* ---- epilogue flags for ffm_gemm_nt ------------------------------------ */
 #define FFM_EPI_BIAS      1   /* + bias[n]                         (fp32 [N])        */

@@ -9,7 +9,7 @@ if [ "$1" = build ]; then
     cd $R/fairfedmed_amd/csrc
     M="-include _gen_rename_main.h"
     for a in 1 2 3; do
-        hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DFFM_SKINNY_ABL=$a -DFFM_SKINNY_NT_DEFAULT=1 $M -c gemm_skinny.hip -o /tmp/gemm_skinny_abl$a.o
+        hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DFFM_SKINNY_ABL=$a $M -c gemm_skinny.hip -o /tmp/gemm_skinny_abl$a.o
         hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/proto/libffm_sk$a.so \
             $(ls *.o | grep -v stamps | grep -v "^gemm_skinny.o") /tmp/gemm_skinny_abl$a.o
     done
