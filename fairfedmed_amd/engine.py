@@ -31,6 +31,7 @@ from ._lib import is16 as _is16
 from . import ops
 from .config import ModelCfg
 from .data import NativeBatch
+from .lora_site import LoraSite
 from .synth import manifest, trainable_keys
 
 Tensor = torch.Tensor
@@ -157,14 +158,6 @@ class SOperands:
             g[self.idx_G.view(-1)] = self.deff.sum(1).view(-1)
 
 
-def _ds_rows(rows: int, N: int, K: int, rank: int, dtype, packed: Optional[bool] = None, dgelu: bool = False) -> int:
-    """dS partial rows a FairLoRA dX GEMM writes (packed=None: the larger of the kernels ffm_gemm_nt may pick)."""
-    fl = L.EPI_LORA | L.EPI_LORA_KR | L.EPI_RANKOP | (L.EPI_DGELU if dgelu else 0)
-    if packed is None:
-        return max(ops.gemm_tiles_m(rows, N, K, fl, rank, dtype, p) for p in (False, True))
-    return ops.gemm_tiles_m(rows, N, K, fl, rank, dtype, packed)
-
-
 @dataclass(frozen=True)
 class Switches:
     """Every Python-side A/B switch of the engines, read from the environment ONCE, when an engine is constructed
@@ -272,7 +265,6 @@ class _Block:
     w_proj: Tensor
     w_proj_t: Tensor
     b_proj: Tensor
-    lora: Optional[Dict[str, str]] = None      # role -> flat key, vision blocks only
     packed: Optional[Dict[str, Tensor]] = None # bf16 vision blocks: the eight weights in MFMA-fragment order (ops.pack_b)
     # bf16 vision blocks, ln_1 folded into the qkv product (FFM_EPI_LNIN): gamma-scaled in_proj weight, its row sums c
     # and d = W beta + b (frozen: built once at load time)
@@ -323,8 +315,8 @@ class _Stack:
         self.causal, self.rank, self.dtype, self.sw = causal, rank, dtype, sw
         self.routes: Dict[int, Route] = {}                   # rows -> tower_route (route())
         # x3: float32 tower whose products run on the bf16 matrix cores as hi/lo pairs (FFM_F32_X3)
-        # (ops.gemm_nt is looked up per call: bench.py wraps it to time the launches)
-
+        # a tower with adapters: (c_fc, c_proj) of every block, made once the frozen weights are loaded (_init_vision_late)
+        self.sites: List[Tuple[LoraSite, LoraSite]] = []
         # x3 (the text tower, 40 token rows): scratch for the products that are split over K across the grid
         # (ffm_gemm_args.sk_part, csrc/gemm_skinny.hip: N = 512 against K = 1536 / 2048 - c_proj forward, dX(c_fc), dX(qkv));
         # one buffer per tower: its launches are ordered on the tower's stream
@@ -366,11 +358,6 @@ class _Stack:
         # sums, consumed by the very next launch - one buffer per tower
         # (ln_1's: two partial rows per head from the attention backward kernels, consumed by dX(qkv))
         self.lnb_part = f(max(8, 2 * heads) * T * 2) if fold else None
-        if rank:
-            self.t1 = [f(T, rank) for _ in range(layers)]
-            self.ts1 = [f(T, rank) for _ in range(layers)]
-            self.t2 = [f(T, rank) for _ in range(layers)]
-            self.ts2 = [f(T, rank) for _ in range(layers)]
         # transient buffers
         self.h = e(T, w)
         self.g = e(T, w)          # running gradient w.r.t. the residual stream
@@ -381,22 +368,12 @@ class _Stack:
         self.dpre = e(T, 4 * w)
         self.delta = f(max_images * heads * tokens)
         if rank:
-            self.u = f(T, rank)
-            # The LoRA-gradient reductions trail the dX chain on a side stream, so everything they
-            # read is kept per layer: gradient of the block output, dL/d(pre), and both us tensors.
+            self.u = f(T, rank)       # u = g B^T of the rank > 16 route: one for all sites (dead once its us is formed)
+            # The LoRA-gradient reductions trail the dX chain on a side stream, so everything they read is kept per layer:
+            # gradient of the block output and dL/d(pre) here, the us vectors and the partial sums in the block's sites.
             self.g_l = [e(T, w) for _ in range(layers)]
             self.dpre_l = [e(T, 4 * w) for _ in range(layers)]
-            self.us2 = [f(T, rank) for _ in range(layers)]
-            self.us1 = [f(T, rank) for _ in range(layers)]
-            # per-layer partial sums of the LoRA gradients; all of them are reduced by ONE launch
-            # (ffm_reduce_partials_multi) at the end of the backward pass
-            ns = ops.lora_grad_splits(T)
-            nb = max(ops.lora_down_blocks_max(T, w, rank, dtype), ops.lora_down_blocks_max(T, 4 * w, rank, dtype),
-                     _ds_rows(T, 4 * w, w, rank, dtype, dgelu=True), _ds_rows(T, w, 4 * w, rank, dtype))
-            self.part = [{"fc_A": f(ns * w * rank), "fc_B": f(ns * 4 * w * rank),
-                          "proj_A": f(ns * 4 * w * rank), "proj_B": f(ns * w * rank),
-                          "fc_S": f(nb * 8 * rank), "proj_S": f(nb * 8 * rank)} for _ in range(layers)]
-            self.plans = {}
+            self.plans = {}                                  # (rows, full backward, block) -> ReducePlan (_reduce_plan)
 
     def route(self, rows: int) -> Route:
         """Which fused kernels serve this tower at `rows` rows (decided once per row count, after the weights are loaded)."""
@@ -407,14 +384,13 @@ class _Stack:
 
     def layer(self, i: int, rows: int) -> _LayerBufs:
         """Block i's share of the stash (everything the backward pass reads), cut to `rows`."""
-        r = self.rank
+        fc, proj = self.sites[i] if self.sites else (None, None)
         return _LayerBufs(self.x[i][:rows], self.xm[i][:rows], self.qkv[i][:rows], self.o[i][:rows], self.h[:rows],
                           self.h2[i][:rows], self.pre[i][:rows], self.act[i][:rows], self.x[i + 1][:rows], self.lse[i],
                           self.st1[i], self.st2[i], self.rowp[i] if self.rowp is not None else None,
                           self.rowp[i + 1] if self.rowp is not None else None,
                           self.rowp2[i] if self.rowp2 is not None else None,
-                          self.t1[i] if r else None, self.ts1[i] if r else None, self.t2[i] if r else None,
-                          self.ts2[i] if r else None)
+                          fc and fc.t, fc and fc.ts, proj and proj.t, proj and proj.ts)
 
 
 class _InferWorkspace:
@@ -656,38 +632,33 @@ class FairLoRAEngine:
             self.dpatch = torch.zeros_like(self.patch_out)
 
     def _init_vision_late(self) -> None:
-        """After the frozen weights are loaded: the packed rank operands of the FairLoRA GEMMs."""
+        """After the frozen weights are loaded: the tower's LoRA sites and the table that packs their rank operands."""
         cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
         ie = "image_encoder.transformer.resblocks."
-        self.sops = SOperands(self.params, [f"{ie}{i}.mlp.c_{n}." for i in range(v.layers) for n in ("fc", "proj")],
-                              cfg, dev)
+        self.sops = SOperands(self.params, [f"{ie}{i}.mlp.c_{n}." for i in range(v.layers) for n in ("fc", "proj")], cfg, dev)
+        st, w, r, h16, T = self.vis, v.width, cfg.lora.rank, _is16(dtype), self.vis.max_rows
+        if not r:
+            return
+        for i, blk in enumerate(st.blocks):
+            # c_fc has ln_2 folded into it (Route.ln2): its rank operand gamma-scaled too, and - ln_2's backward fold
+            # (Route.ln2_bwd) - the rank operand of dX(c_fc) carries W gamma and W beta + b as rows 14 / 15: its t[14] / t[15]
+            # are the two row sums against those vectors, out of the matrix cores; every consumer masks the slots beyond r
+            fc = LoraSite(self, f"{ie}{i}.mlp.c_fc.", w, 4 * w, T, u=st.u, wide=h16, ln=(blk.ln2_w, blk.ln2_b) if h16 else None,
+                          row1415=(blk.c_fc, blk.d_fc) if (h16 and blk.c_fc is not None and r <= 14) else None)
+            proj = LoraSite(self, f"{ie}{i}.mlp.c_proj.", 4 * w, w, T, u=st.u, wide=h16)
+            st.sites.append((fc, proj))
+        # dS partials: one size for the tower, the largest of ffm_lora_down's blocks and of the row tiles of either kernel
+        # ffm_gemm_nt may pick for the two dX products (c_proj's carries the dGELU)
+        nb = max([ops.lora_down_blocks_max(T, s.N, r, dtype) for s in (fc, proj)]
+                 + [s.ds_tiles(T, p, dgelu=s is proj) for s in (fc, proj) for p in (False, True)])
+        for s in (s for pair in st.sites for s in pair):
+            s.alloc_ds(nb * 8 * r)
         if self.fused_rank:
-            w = v.width
+            # one table for all blocks, in the order (fc A, proj A, fc B, proj B, fc A with ln_2) per block
             ent = []
-            self.rk = []
-            self.lw_wide = []
-            for blk in self.vis.blocks:
-                pk = {"fc_A": torch.zeros(16, w, device=dev, dtype=dtype),
-                      "proj_A": torch.zeros(16, 4 * w, device=dev, dtype=dtype),
-                      "fc_B": torch.zeros(16, 4 * w, device=dev, dtype=dtype),
-                      "proj_B": torch.zeros(16, w, device=dev, dtype=dtype)}
-                self.rk.append(pk)
-                # the same matrices as [K, 32] rows: the `lw` operand of the GEMM whose OUTPUT columns they span
-                wd = {role: torch.zeros(buf.shape[1], 32, device=dev, dtype=dtype) for role, buf in pk.items()} \
-                    if _is16(dtype) else {}
-                self.lw_wide.append(wd)
-                for role, buf in pk.items():
-                    # ln_2's backward fold (Route.ln2_bwd): the rank operand of dX(c_fc) carries W gamma and W beta + b as rows
-                    # 14 / 15 - its t[14] / t[15] are the two row sums against those vectors, out of the matrix cores; every
-                    # consumer masks the slots beyond r (rank <= 14)
-                    extra = (blk.c_fc, blk.d_fc) if (role == "fc_B" and _is16(dtype) and blk.c_fc is not None and cfg.lora.rank <= 14) else None
-                    ent.append((self.params.view(blk.lora[role]), role.endswith("_B"), buf, wd.get(role), None, extra))
-                if _is16(dtype):
-                    # ln_2 folded into c_fc: the rank operand gamma-scaled, and its two correction rows (ops.LnIn.rk)
-                    pk["fc_A_ln"] = torch.zeros(16, w, device=dev, dtype=dtype)
-                    pk["fc_A_lnrk"] = torch.zeros(32, device=dev, dtype=torch.float32)
-                    ent.append((self.params.view(blk.lora["fc_A"]), False, pk["fc_A_ln"], None,
-                                (blk.ln2_w, blk.ln2_b, pk["fc_A_lnrk"])))
+            for fc, proj in st.sites:
+                (fa, fb, *fln), (pa, pb) = fc.pack_entries(), proj.pack_entries()
+                ent += [fa, pa, fb, pb, *fln]
             self.pack_plan = ops.PackPlan(ent, dtype, dev)
 
     def _init_infer(self) -> None:
@@ -740,8 +711,6 @@ class FairLoRAEngine:
                 blk.w_fc_ln = W(wf32 * blk.ln2_w[None, :])
                 blk.c_fc = blk.w_fc_ln.float().sum(1).contiguous()
                 blk.d_fc = (wf32 @ blk.ln2_b + blk.b_fc).contiguous()
-            if lora:
-                blk.lora = {f"{n}_{m}": f"{p}mlp.c_{n}.lora_{m}.weight" for n in ("fc", "proj") for m in "ASB"}
             if old is not None:
                 # keep the device addresses stable (recorded launch plans hold raw pointers): refresh in place
                 for name, val in vars(blk).items():
@@ -801,22 +770,12 @@ class FairLoRAEngine:
                     self.pk_out[name] = ops.pack_b(w, self.pk_out.get(name))
 
     # -------------------------------------------------------------- tower --
-    def _lora_view(self, blk: _Block, role: str) -> Tensor:
-        return self.params.view(blk.lora[role])
-
-    def _S(self, layer: int, which: str) -> Tensor:
-        return self.sops.op(f"image_encoder.transformer.resblocks.{layer}.mlp.c_{which}.")
-
-    def _dS(self, layer: int, which: str) -> Tensor:
-        return self.sops.grad(f"image_encoder.transformer.resblocks.{layer}.mlp.c_{which}.")
-
     def _stack_forward(self, st: _Stack, rows: int, images: int, attr: Optional[Tensor], rows_per_sample: int,
                        bufs=None) -> Tensor:
         """The tower input is in layer 0's `x`; returns the tower output view.  bufs: the provider of every block's
         `_LayerBufs` - the tower's own stash (default: training and forward()) or an `_InferWorkspace`, whose sets have no
         pre-activation, no rank vectors and no statistics: the same launches in the same order, fewer stores."""
-        lo = self.cfg.lora
-        r, G = st.rank, lo.num_groups
+        r = st.rank
         gemm = st.gemm
         bufs = st if bufs is None else bufs
         out = lb = None
@@ -845,31 +804,23 @@ class FairLoRAEngine:
             gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=lb.rowp2 if fold2 else None)
             if not fold2:
                 ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, lb.st2[0], lb.st2[1])
+            sfc, sproj = st.sites[i] if r else (None, None)
             if r and self.fused_rank:
+                ro = sfc.rank_fwd(attr, rows_per_sample, lb.t1, lb.ts1, ln=bool(fold2))
                 if fold2:
                     # ln_2 rides inside the c_fc product (h2 is never written; dA(c_fc) takes the raw rows, _stack_backward)
-                    ro = ops.RankOp(self.rk[i]["fc_A_ln"], self._S(i, "fc"), attr, rows_per_sample, lo.scaling,
-                                    lo.lambda_group, t_out=lb.t1, ts_out=lb.ts1, lw_wide=self.lw_wide[i].get("fc_B"))
-                    ln = ops.LnIn(lb.rowp2, fold2, blk.c_fc, lb.st2[0], lb.st2[1], rk=self.rk[i]["fc_A_lnrk"])
-                    fc(xm, blk.w_fc_ln, bias=blk.d_fc, lw=self._lora_view(blk, "fc_B"), rankop=ro,
-                       b_packed=blk.pk("w_fc_ln"), ln_in=ln)
+                    ln = ops.LnIn(lb.rowp2, fold2, blk.c_fc, lb.st2[0], lb.st2[1], rk=sfc.lnrk)
+                    fc(xm, blk.w_fc_ln, bias=blk.d_fc, lw=sfc.B, rankop=ro, b_packed=blk.pk("w_fc_ln"), ln_in=ln)
                 else:
-                    ro = ops.RankOp(self.rk[i]["fc_A"], self._S(i, "fc"), attr, rows_per_sample, lo.scaling,
-                                    lo.lambda_group, t_out=lb.t1, ts_out=lb.ts1, lw_wide=self.lw_wide[i].get("fc_B"))
-                    fc(h2, blk.w_fc, bias=blk.b_fc, lw=self._lora_view(blk, "fc_B"), rankop=ro, b_packed=blk.pk("w_fc"))
-                ro = ops.RankOp(self.rk[i]["proj_A"], self._S(i, "proj"), attr, rows_per_sample,
-                                lo.scaling, lo.lambda_group, t_out=lb.t2, ts_out=lb.ts2,
-                                lw_wide=self.lw_wide[i].get("proj_B"))
-                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, lw=self._lora_view(blk, "proj_B"),
-                     res=xm, rankop=ro, b_packed=blk.pk("w_proj"),
+                    fc(h2, blk.w_fc, bias=blk.b_fc, lw=sfc.B, rankop=ro, b_packed=blk.pk("w_fc"))
+                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, lw=sproj.B, res=xm,
+                     rankop=sproj.rank_fwd(attr, rows_per_sample, lb.t2, lb.ts2), b_packed=blk.pk("w_proj"),
                      rowstats=lb.rowp_out if (fold and i + 1 < st.layers) else None)
             elif r:
-                ops.lora_down(h2, self._lora_view(blk, "fc_A"), False, self._S(i, "fc"), attr, r, G,
-                              rows_per_sample, lo.scaling, lo.lambda_group, lb.t1, lb.ts1)
-                fc(h2, blk.w_fc, bias=blk.b_fc, ts=lb.ts1, lw=self._lora_view(blk, "fc_B"))
-                ops.lora_down(act, self._lora_view(blk, "proj_A"), False, self._S(i, "proj"), attr, r, G,
-                              rows_per_sample, lo.scaling, lo.lambda_group, lb.t2, lb.ts2)
-                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, ts=lb.ts2, lw=self._lora_view(blk, "proj_B"), res=xm)
+                sfc.down_fwd(h2, attr, rows_per_sample, lb.t1, lb.ts1)
+                fc(h2, blk.w_fc, bias=blk.b_fc, ts=lb.ts1, lw=sfc.B)
+                sproj.down_fwd(act, attr, rows_per_sample, lb.t2, lb.ts2)
+                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, ts=lb.ts2, lw=sproj.B, res=xm)
             else:
                 fc(h2, blk.w_fc, bias=blk.b_fc)
                 gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, res=xm)
@@ -881,8 +832,7 @@ class FairLoRAEngine:
         """st.g[:rows] holds dL/d(tower output) (a FairLoRA tower with grad_in_last: st.g_l[layers - 1] does - the buffer the
         last block's reductions read - and no copy is made); on return st.g holds dL/d(tower input) (if need_input_grad).
         LoRA gradients are written into params.grad."""
-        lo = self.cfg.lora
-        r, G, w = st.rank, lo.num_groups, st.width
+        r = st.rank
         gemm = st.gemm
         g, g1 = st.g[:rows], st.g1[:rows]
         main = torch.cuda.current_stream(self.device)
@@ -897,8 +847,7 @@ class FairLoRAEngine:
                 gi, dpre = st.g_l[i][:rows], st.dpre_l[i][:rows]
                 if i == st.layers - 1 and not grad_in_last:
                     self._glue(lambda gi=gi, g=g: gi.copy_(g))
-                u, us2, us1 = st.u[:rows], st.us2[i][:rows], st.us1[i][:rows]
-                pt = st.part[i]
+                sfc, sproj = st.sites[i]
                 # ---- critical path: u = g B^T and dX (+ LoRA dx term), dS partials
                 fused = self.fused_rank
                 if last:
@@ -907,7 +856,7 @@ class FairLoRAEngine:
                     self._ev_record(self.ev_tail0, main)
                     self._ev_wait(self.grad_stream, self.ev_tail0)
                     with self._on(self.grad_stream):
-                        ops.lora_grad_partial(gi, st.ts2[i][:rows], r, pt["proj_B"])
+                        sproj.grad_B(gi)
                 # FFM_EPI_LGRAD: dB(c_fc) = dpre^T ts1 and dA(c_proj) = act^T us2 leave with the dX product of c_proj, which
                 # holds dpre and (through pre) act in registers - per row tile, into the buffers the two reduction launches
                 # they replace would have filled (77 MB per block that the side stream no longer reads beside the chain)
@@ -915,32 +864,21 @@ class FairLoRAEngine:
                 # ln_2's backward rides in this block's two dX products (not block 0 of a tower that stops there)
                 lnb = 0 if last else rt.ln2_bwd
                 if fused:
-                    ro = ops.RankOp(self.rk[i]["proj_B"], self._S(i, "proj"), attr, rows_per_sample,
-                                    lo.scaling, lo.lambda_group, ts_out=us2, t_fwd=st.t2[i][:rows], ds_part=pt["proj_S"],
-                                    lw_wide=self.lw_wide[i].get("proj_A"),
-                                    lgrad=(st.ts1[i][:rows], pt["fc_B"], pt["proj_A"]) if lg else None)
-                    gemm(gi, blk.w_proj_t, dpre, lw=self._lora_view(blk, "proj_A"), lw_is_kr=True,
-                                dgelu_aux=pre, rankop=ro, b_packed=blk.pk("w_proj_t"),
-                                lnb_stat=ops.LnBwdStat(st.lnb_part) if lnb else None)
+                    ro = sproj.rank_bwd(attr, rows_per_sample, rows, lgrad=(sfc.ts[:rows], sfc.pB, sproj.pA) if lg else None)
+                    gemm(gi, blk.w_proj_t, dpre, lw=sproj.A, lw_is_kr=True, dgelu_aux=pre, rankop=ro,
+                         b_packed=blk.pk("w_proj_t"), lnb_stat=ops.LnBwdStat(st.lnb_part) if lnb else None)
                 else:
-                    ops.lora_down(gi, self._lora_view(blk, "proj_B"), True, self._S(i, "proj"), attr, r, G,
-                                  rows_per_sample, lo.scaling, lo.lambda_group, u, us2, st.t2[i][:rows], pt["proj_S"])
-                    gemm(gi, blk.w_proj_t, dpre, ts=us2, lw=self._lora_view(blk, "proj_A"), lw_is_kr=True,
-                                dgelu_aux=pre)
+                    sproj.down_bwd(gi, attr, rows_per_sample)
+                    gemm(gi, blk.w_proj_t, dpre, ts=sproj.us[:rows], lw=sproj.A, lw_is_kr=True, dgelu_aux=pre)
                 if fused and not last:
                     # u1 = dpre B_fc^T rides inside the dX GEMM of c_fc
-                    ro = ops.RankOp(self.rk[i]["fc_B"], self._S(i, "fc"), attr, rows_per_sample,
-                                    lo.scaling, lo.lambda_group, ts_out=us1, t_fwd=st.t1[i][:rows], ds_part=pt["fc_S"],
-                                    lw_wide=self.lw_wide[i].get("fc_A"))
+                    ro = sfc.rank_bwd(attr, rows_per_sample, rows)
                     if lnb:
                         # ... and stores dL/d x_mid = LayerNorm backward(g_h) + gi directly: no ffm_layernorm_bwd launch
-                        gemm(dpre, blk.w_fc_t, g1, lw=self._lora_view(blk, "fc_A"), lw_is_kr=True, rankop=ro,
-                             b_packed=blk.pk("w_fc_t"),
-                             lnb_apply=ops.LnBwdApply(st.lnb_part, lnb, xm, blk.ln2_w, st.st2[i][0], st.st2[i][1],
-                                                      self.rk[i]["fc_A_lnrk"], gi))
+                        gemm(dpre, blk.w_fc_t, g1, lw=sfc.A, lw_is_kr=True, rankop=ro, b_packed=blk.pk("w_fc_t"),
+                             lnb_apply=ops.LnBwdApply(st.lnb_part, lnb, xm, blk.ln2_w, st.st2[i][0], st.st2[i][1], sfc.lnrk, gi))
                     else:
-                        gemm(dpre, blk.w_fc_t, st.dh[:rows], lw=self._lora_view(blk, "fc_A"), lw_is_kr=True,
-                             rankop=ro, b_packed=blk.pk("w_fc_t"))
+                        gemm(dpre, blk.w_fc_t, st.dh[:rows], lw=sfc.A, lw_is_kr=True, rankop=ro, b_packed=blk.pk("w_fc_t"))
                 else:
                     if last:
                         # the dX chain ends with this down projection: the three reductions that do not need its result
@@ -949,26 +887,25 @@ class FairLoRAEngine:
                         self._ev_wait(self.grad_stream, self.ev_tail)
                         with self._on(self.grad_stream):
                             if not lg:
-                                ops.lora_grad_partial(act, us2, r, pt["proj_A"])
-                                ops.lora_grad_partial(dpre, st.ts1[i][:rows], r, pt["fc_B"])
-                    ops.lora_down(dpre, self._lora_view(blk, "fc_B"), True, self._S(i, "fc"), attr, r, G,
-                                  rows_per_sample, lo.scaling, lo.lambda_group, u, us1, st.t1[i][:rows], pt["fc_S"])
+                                sproj.grad_A(act)
+                                sfc.grad_B(dpre)
+                    sfc.down_bwd(dpre, attr, rows_per_sample)
                 # ---- off the critical path: the four rank-r gradient reductions of this block
-                def reductions(i=i, blk=blk, gi=gi, act=act, dpre=dpre, us2=us2, us1=us1, pt=pt, xm=xm, h2=h2, last=last, lg=lg):
+                def reductions(i=i, sfc=sfc, sproj=sproj, gi=gi, act=act, dpre=dpre, xm=xm, h2=h2, last=last, lg=lg):
                     # (the step's tail - block 0's last reduction and the sum of its partials - on the chain's own stream
                     # instead of behind two cross-stream events: measured, 4.699 -> 4.692 ms per step, nothing; not kept)
                     self._ev_record(self.ev_layer[i], main)
                     self._ev_wait(self.grad_stream, self.ev_layer[i])
                     with self._on(self.grad_stream):
                         if not last:
-                            ops.lora_grad_partial(gi, st.ts2[i][:rows], r, pt["proj_B"])
+                            sproj.grad_B(gi)
                             if not lg:
-                                ops.lora_grad_partial(act, us2, r, pt["proj_A"])
-                                ops.lora_grad_partial(dpre, st.ts1[i][:rows], r, pt["fc_B"])
+                                sproj.grad_A(act)
+                                sfc.grad_B(dpre)
                         if rt.ln2:
-                            ops.lora_grad_partial_ln(xm, us1, st.st2[i][0], st.st2[i][1], blk.ln2_w, blk.ln2_b, r, pt["fc_A"])
+                            sfc.grad_A(xm, ln_stats=st.st2[i])
                         else:
-                            ops.lora_grad_partial(h2, us1, r, pt["fc_A"])
+                            sfc.grad_A(h2)
                         # this block's six gradient tensors are complete: sum their partials now, behind the four reductions
                         # on the same side stream (one launch per block; only block 0's is left when the dX chain ends -
                         # ONE launch for all 72 tensors at the end sat in the step's tail for ~50 us)
@@ -983,8 +920,7 @@ class FairLoRAEngine:
                 if last:
                     break
                 if not fused:
-                    gemm(dpre, blk.w_fc_t, st.dh[:rows], ts=us1, lw=self._lora_view(blk, "fc_A"),
-                                lw_is_kr=True)
+                    gemm(dpre, blk.w_fc_t, st.dh[:rows], ts=sfc.us[:rows], lw=sfc.A, lw_is_kr=True)
                 gout = st.g_l[i - 1][:rows] if i > 0 else g
             else:
                 gi, dpre, gout = g, st.dpre[:rows], g
@@ -1021,24 +957,14 @@ class FairLoRAEngine:
         """Descriptor table (built once per row count and block) that sums the block's partials into params.grad."""
         key = (rows, full_bwd, layer)
         if key not in st.plans:
-            r, G, w = st.rank, self.cfg.lora.num_groups, st.width
-            nsp = ops.lora_grad_splits(rows)
-            li, blk, pt = layer, st.blocks[layer], st.part[layer]
-            gv = lambda role: self.params.view(blk.lora[role], "grad")
-            # dS partial rows: GEMM row tiles when the down projection is fused, lora_down blocks otherwise
-            # (block 0's c_fc has no dX GEMM, so it always uses the stand-alone kernel)
-            # dS partial rows written by the dX GEMMs (c_proj: N = 4w, K = w; c_fc: N = w, K = 4w)
-            pk = blk.packed is not None
-            nb_p = _ds_rows(rows, 4 * w, w, r, self.dtype, pk, dgelu=True) if self.fused_rank \
-                else ops.lora_down_blocks(rows, w, r, self.dtype)
-            nb_f = _ds_rows(rows, w, 4 * w, r, self.dtype, pk) if (self.fused_rank and (li > 0 or full_bwd)) \
-                else ops.lora_down_blocks(rows, 4 * w, r, self.dtype)
-            # (FFM_EPI_LGRAD: proj_A and fc_B hold one partial per row tile of the dX product of c_proj)
-            nlg = st.route(rows).lgrad or nsp
-            ent = [(pt["proj_S"], nb_p, G * r, self._dS(li, "proj"), 0, 0), (pt["fc_S"], nb_f, G * r, self._dS(li, "fc"), 0, 0),
-                   (pt["proj_B"], nsp, w * r, gv("proj_B"), w, r), (pt["proj_A"], nlg, 4 * w * r, gv("proj_A"), 0, 0),
-                   (pt["fc_B"], nlg, 4 * w * r, gv("fc_B"), 4 * w, r), (pt["fc_A"], nsp, w * r, gv("fc_A"), 0, 0)]
-            st.plans[key] = ops.ReducePlan(ent, self.device)
+            (fc, proj), pk = st.sites[layer], st.blocks[layer].packed is not None
+            # (FFM_EPI_LGRAD: dA(c_proj) and dB(c_fc) hold one partial per row tile of the dX product of c_proj)
+            nlg = st.route(rows).lgrad or None
+            # dS partial rows: those of the dX product that carries the down projection (c_proj's also the dGELU); block 0's
+            # c_fc has no dX product where the chain ends there, and takes the stand-alone kernel
+            pb, pa, ps = proj.reduce_entries(rows, proj.ds_rows(rows, pk, dgelu=True), splits_A=nlg)
+            fb, fa, fs = fc.reduce_entries(rows, fc.ds_rows(rows, pk, gemm=layer > 0 or full_bwd), splits_B=nlg)
+            st.plans[key] = ops.ReducePlan([ps, fs, pb, pa, fb, fa], self.device)
         return st.plans[key]
 
     # ------------------------------------------------------------ replay --

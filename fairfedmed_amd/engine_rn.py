@@ -20,98 +20,56 @@ import torch
 
 from . import ops
 from ._lib import is16 as _is16
-from .engine import FairLoRAEngine, _round_up
+from .engine import FairLoRAEngine, SOperands, _round_up
+from .lora_site import LoraSite
 from .synth import buffer_keys
 
 Tensor = torch.Tensor
 
 
-class _Lora:
-    """One (Fair)LoRA-wrapped linear over token / pixel rows: y = x W^T (+b) + scaling ((x A) * s_b) B.
-    fair=False is the reference's LoRALinear (:218-241): the same update with s = 1 and no groups."""
+class _Lora(LoraSite):
+    """A site of the RN50 tower: it sizes its own dS partials, joins the engine's pack table, and wraps the product
+    (fwd / bwd) and its two reductions (grads) around the site's operands."""
 
     def __init__(self, eng: "RN50Engine", prefix: str, K: int, N: int, max_rows: int, fair: bool):
-        self.eng, self.K, self.N, self.fair = eng, K, N, fair
-        self.kA, self.kB = prefix + "lora_A.weight", prefix + "lora_B.weight"
-        self.kS = prefix + "lora_S.weight" if fair else None
-        self.prefix = prefix
-        lo, dt = eng.cfg.lora, eng.dtype
-        r = lo.rank
-        f = lambda *s: torch.zeros(*s, device=eng.device, dtype=torch.float32)
-        self.t, self.ts, self.u, self.us = f(max_rows, r), f(max_rows, r), f(max_rows, r), f(max_rows, r)
-        ns = ops.lora_grad_splits(max_rows)
-        self.pA, self.pB = f(ns * K * r), f(ns * N * r)
-        # rank <= 16: the down projections ride inside the GEMMs (FFM_EPI_RANKOP); their operands are the LoRA
-        # matrices re-packed to [16, K] in the compute dtype once per step (one launch for all sites)
-        self.fused = 0 < r <= 16
-        nb = ops.lora_down_blocks_max(max_rows, N, r, dt)
+        super().__init__(eng, prefix, K, N, max_rows, fair)
+        lo = eng.cfg.lora
+        nb = ops.lora_down_blocks_max(max_rows, N, lo.rank, eng.dtype)
         if self.fused:
-            nb = max(nb, self._tiles(max_rows))
-            self.rkA = torch.zeros(16, K, device=eng.device, dtype=dt)
-            self.rkB = torch.zeros(16, N, device=eng.device, dtype=dt)
-            eng.pack_entries += [(eng.params.view(self.kA), False, self.rkA), (eng.params.view(self.kB), True, self.rkB)]
-        self.pS = f(nb * lo.num_groups * r) if fair else None
-
-    def _tiles(self, rows: int) -> int:
-        """dS partial rows the dX GEMM (M = rows, N = in features, K = out features) writes."""
-        from . import _lib as L
-        return ops.gemm_tiles_m(rows, self.K, self.N, L.EPI_LORA | L.EPI_LORA_KR | L.EPI_RANKOP, self.eng.cfg.lora.rank,
-                                self.eng.dtype, False)
-
-    def _s(self) -> Tuple[Tensor, int]:
-        e = self.eng
-        return (e.sops.op(self.prefix), e.cfg.lora.num_groups) if self.fair else (e.ones_s, 1)
+            nb = max(nb, self.ds_tiles(max_rows))
+            eng.pack_entries += self.pack_entries()
+        if fair:
+            self.alloc_ds(nb * lo.num_groups * lo.rank)
 
     def fwd(self, x: Tensor, W: Tensor, out: Tensor, attr: Optional[Tensor], rps: int, bias=None, res=None,
             colstats: Optional[Tensor] = None) -> None:
         """colstats: the GEMM also leaves the column sums of its row tiles there (the BatchNorm that follows)."""
-        e, lo = self.eng, self.eng.cfg.lora
         rows = x.shape[0]
-        S, G = self._s()
-        attr = attr if self.fair else None
+        t, ts = self.t[:rows], self.ts[:rows]
         if self.fused:
-            ro = ops.RankOp(self.rkA, S, attr, rps, lo.scaling, lo.lambda_group, t_out=self.t[:rows], ts_out=self.ts[:rows])
-            ops.gemm_nt(x, W, out, bias=bias, lw=e.params.view(self.kB), res=res, rankop=ro, colstats=colstats)
+            ops.gemm_nt(x, W, out, bias=bias, lw=self.B, res=res, rankop=self.rank_fwd(attr, rps, t, ts), colstats=colstats)
             return
-        ops.lora_down(x, e.params.view(self.kA), False, S, attr, lo.rank, G, rps, lo.scaling,
-                      lo.lambda_group, self.t[:rows], self.ts[:rows])
-        ops.gemm_nt(x, W, out, bias=bias, ts=self.ts[:rows], lw=e.params.view(self.kB), res=res, colstats=colstats)
+        self.down_fwd(x, attr, rps, t, ts)
+        ops.gemm_nt(x, W, out, bias=bias, ts=ts, lw=self.B, res=res, colstats=colstats)
 
     def bwd(self, g: Tensor, Wt: Tensor, dx: Tensor, attr: Optional[Tensor], rps: int, res=None,
             bnbwd=None, colstats: Optional[Tensor] = None) -> None:
         """g = dL/dy; writes dx = g W (+ LoRA term) (+ res) and the partial sums of dS; the caller runs grads() (dA, dB)
         itself, on the gradient stream.  bnbwd / colstats (fused sites only): dx is the gradient of a BatchNorm
         output, and the product's epilogue leaves that BatchNorm's backward column sums in colstats (ops.gemm_nt)."""
-        e, lo = self.eng, self.eng.cfg.lora
         rows = g.shape[0]
-        S, G = self._s()
-        attr = attr if self.fair else None
         if self.fused:
-            ro = ops.RankOp(self.rkB, S, attr, rps, lo.scaling, lo.lambda_group, ts_out=self.us[:rows],
-                            t_fwd=self.t[:rows] if self.fair else None, ds_part=self.pS)
-            ops.gemm_nt(g, Wt, dx, lw=e.params.view(self.kA), lw_is_kr=True, res=res, rankop=ro, bnbwd=bnbwd,
+            ops.gemm_nt(g, Wt, dx, lw=self.A, lw_is_kr=True, res=res, rankop=self.rank_bwd(attr, rps, rows), bnbwd=bnbwd,
                         colstats=colstats)
         else:
             assert bnbwd is None
-            ops.lora_down(g, e.params.view(self.kB), True, S, attr, lo.rank, G, rps, lo.scaling,
-                          lo.lambda_group, self.u[:rows], self.us[:rows], self.t[:rows] if self.fair else None, self.pS)
-            ops.gemm_nt(g, Wt, dx, ts=self.us[:rows], lw=e.params.view(self.kA), lw_is_kr=True, res=res)
+            self.down_bwd(g, attr, rps)
+            ops.gemm_nt(g, Wt, dx, ts=self.us[:rows], lw=self.A, lw_is_kr=True, res=res)
 
     def grads(self, g: Tensor, x: Tensor) -> None:
         """The rank-r reductions dB = g^T ts, dA = x^T us (partials); nothing downstream of them in the dX chain."""
-        rows, r = g.shape[0], self.eng.cfg.lora.rank
-        ops.lora_grad_partial(g, self.ts[:rows], r, self.pB)
-        ops.lora_grad_partial(x, self.us[:rows], r, self.pA)
-
-    def reduce_entries(self, rows: int) -> list:
-        e, lo = self.eng, self.eng.cfg.lora
-        r, nsp = lo.rank, ops.lora_grad_splits(rows)
-        gv = lambda k: e.params.view(k, "grad")
-        ent = [(self.pB, nsp, self.N * r, gv(self.kB), self.N, r), (self.pA, nsp, self.K * r, gv(self.kA), 0, 0)]
-        if self.fair:
-            nb = self._tiles(rows) if self.fused else ops.lora_down_blocks(rows, self.N, r, e.dtype)
-            ent.append((self.pS, nb, lo.num_groups * r, e.sops.grad(self.prefix), 0, 0))
-        return ent
+        self.grad_B(g)
+        self.grad_A(x)
 
 
 class _BN:
@@ -404,7 +362,6 @@ class RN50Engine(FairLoRAEngine):
         self.nbt = torch.zeros(len(self.bns), device=dev, dtype=torch.int64)
 
     def _init_vision_late(self) -> None:
-        from .engine import SOperands
         if getattr(self.cfg.lora, "lora_type", "FairLoRA") != "FairLoRA":
             raise NotImplementedError(self.cfg.lora.lora_type)    # trainers/GLP_OT_SVLoRA.py:561-567: ResNet knows FairLoRA only
         self.sops = SOperands(self.params, [site.prefix for blk in self.blocks for site, _ in blk.loras()], self.cfg,
