@@ -133,7 +133,7 @@ def model_cfg_from_reference(cfg, classnames: Sequence[str], clip_sd: Dict[str, 
             from .trainer import ATTRIBUTE_GROUPS
             G = len(ATTRIBUTE_GROUPS[cfg.DATASET.NAME][cfg.DATASET.ATTRIBUTE_TYPE])
         lo = C.LoraCfg(rank=lora.RANK, alpha=lora.ALPHA, num_groups=G, lora_type=ltype,
-                       global_s=bool(getattr(lora, "GLOBAL_S", False)))
+                       global_s=bool(getattr(lora, "GLOBAL_S", False)), targets=str(getattr(lora, "TARGETS", "mlp")))
     else:
         raise NotImplementedError("UNFREEZE_IMAGE_ENCODER must be set: without it no adapter is injected")
     return C.ModelCfg(vision=vision, text=text, lora=lo, n_prompts=got.N, n_ctx=got.N_CTX, n_cls=len(classnames),

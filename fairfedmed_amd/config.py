@@ -77,6 +77,9 @@ class TextCfg:
     layers: int = 12
 
 
+LORA_TARGETS = ("mlp", "attn", "mlp+attn")
+
+
 @dataclass(frozen=True)
 class LoraCfg:
     rank: int = 8
@@ -90,6 +93,22 @@ class LoraCfg:
     # TRAINER.GLP_OT_LORA.GLOBAL_S: one more trainable vector lora_S_global [r] (1-D after reset_parameters,
     # :418-422 / :300-304) added to every sample's singular values: s_b = pi_b S + S_global
     global_s: bool = False
+    # Which linears of a vision block carry an adapter: 'mlp' (the reference: mlp.c_fc / mlp.c_proj,
+    # trainers/GLP_OT_SVLoRA.py:516), 'attn' (an extension: the packed in-projection and the out-projection of the
+    # attention) or 'mlp+attn'.  ViT towers only; the text tower never carries adapters.
+    targets: str = "mlp"
+
+    def __post_init__(self):
+        if self.targets not in LORA_TARGETS:
+            raise ValueError(f"lora targets must be one of {LORA_TARGETS}, got {self.targets!r}")
+
+    @property
+    def on_mlp(self) -> bool:
+        return "mlp" in self.targets.split("+")
+
+    @property
+    def on_attn(self) -> bool:
+        return "attn" in self.targets.split("+")
 
     @property
     def scaling(self) -> float:  # trainers/GLP_OT_SVLoRA.py:346

@@ -28,6 +28,7 @@ struct ffm_panel_cfg {
     int min_k;       // not selected for a shorter K (0: no limit of its own)
     int unit;        // the translation unit that instantiates the row: 0 gemm_panel.hip (plain), 1 / 2 / 3 gemm_panel_rk /
                      // _rk2 / _rk3.hip (FairLoRA: split for compile time, one unit took 6.5 minutes)
+    bool lora_plain = false;  // has the FairLoRA word without GELU or residual (the adapted qkv forward, N = 3 x width)
 };
 constexpr int FFM_PANEL_NCFG = 13;
 constexpr ffm_panel_cfg FFM_PANEL_CFGS[FFM_PANEL_NCFG] = {
@@ -42,7 +43,10 @@ constexpr ffm_panel_cfg FFM_PANEL_CFGS[FFM_PANEL_NCFG] = {
     // two waves per SIMD: the same tiles as 3, 2 (5, 6: eight column slabs, no gain, twice the LDS fragment reads) and 0
     {11, 1, true, 1, 8, 0, false, true, false, false, 0, 1},    //  5: 176x128 FairLoRA
     {10, 1, false, 1, 8, 0, false, true, false, false, 0, 0},   //  6: 160x128 plain
-    {13, 3, true, 1, 8, 0, true, true, true, false, 0, 3},      //  7: 208x384 FairLoRA
+    // (7 also serves the adapted in-projection with ln_1 folded in: 186 blocks at 6304 x 2304, where the 128-column FairLoRA
+    // tiles need 720.  The same product WITHOUT the fold, FFM_EPI_BIAS | FFM_EPI_LORA, measured 40.0 us on this tile against
+    // 39.6 us on the 128x128 kernel (tools/bench_panel.py --attn) and has no panel word)
+    {13, 3, true, 1, 8, 0, true, true, true, false, 0, 3, true}, //  7: 208x384 FairLoRA
     // 8: the 160-row FairLoRA tile for N = 768 (240 blocks at 6304 rows where the 176-row tile launches 216); 9 / 10:
     // 240 x 256 for qkv (243 blocks), one and two waves per SIMD
     {10, 2, true, 1, 4, 0, true, true, false, true, 0, 2},      //  8: 160x128 FairLoRA
@@ -76,6 +80,7 @@ constexpr ffm_panel_tile ffm_panel_tile_of(const ffm_panel_cfg& c) {
     X(FFM_EPI_BIAS | FFM_EPI_LNIN)                        /* qkv forward with ln_1 folded in */                         \
     X(FFM_EPI_LNB_APPLY)                                  /* dX of qkv applying ln_1's backward */
 #define FFM_PANEL_EPI_RK(X)                                                                                             \
+    X(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_LNIN)       /* adapted qkv forward with ln_1 folded in (rows with lora_plain) */ \
     X(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)                           /* c_fc forward */                          \
     X(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_LNIN)            /* ... with ln_2 folded in */               \
     X(FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)                       /* c_proj forward */                        \
@@ -102,6 +107,7 @@ constexpr bool ffm_panel_has(int c, int f) {
     if ((f & FFM_EPI_ROWSTATS) && ((2 * cf.nf) & (2 * cf.nf - 1))) return false;      // row sums: power-of-two lanes per row
     if ((f & FFM_EPI_LGRAD) && !cf.lgrad) return false;
     if ((f & FFM_EPI_LNB_APPLY) && !cf.lnb_apply) return false;
+    if (cf.rankop && !(f & (FFM_EPI_GELU | FFM_EPI_RESIDUAL | FFM_EPI_LORA_KR)) && !cf.lora_plain) return false;
     return true;
 }
 

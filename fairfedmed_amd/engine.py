@@ -193,17 +193,34 @@ class Route:
     red_at: int = 0       # where the side stream starts a block's LoRA-gradient reductions (_stack_backward)
 
 
+@dataclass(frozen=True)
+class Targets:
+    """Which linears of a tower's blocks carry an adapter (LoraCfg.targets): what the attention sites add to routing.
+    A record of its own - Route keeps its fields for every tower - and the `targets` keyword of tower_route."""
+    mlp: bool = True      # mlp.c_fc / mlp.c_proj (the reference's placement)
+    attn: bool = False    # attn.in_proj / attn.out_proj
+
+    @classmethod
+    def of(cls, lora_cfg) -> "Targets":
+        return cls(lora_cfg.on_mlp, lora_cfg.on_attn)
+
+
 def _can_fold(rank: int, dtype) -> bool:
     """A tower can take a fold at all (it owns the partial-sum buffers rowp / rowp2 / lnb_part): adapters, 16-bit storage."""
     return bool(rank) and _is16(dtype)
 
 
 def tower_route(width: int, heads: int, tokens: int, causal: bool, rank: int, dtype, packed: bool, rows: int,
-                sw: Switches) -> Route:
+                sw: Switches, targets: Targets = Targets()) -> Route:
     """The route of a tower of this geometry at `rows` rows: a pure function of its arguments and of the library's host-side
     queries (which kernel ffm_gemm_nt picks for a shape, and how it tiles it) - no GPU, no engine.  Every fold needs the
     panel kernel with the folding epilogue for EACH product it touches at this row count, the rank inside one MFMA tile
-    (0 < rank <= 16: FFM_EPI_RANKOP) and 16-bit storage; tests/test_route_cpu.py pins the regimes of ViT-B/16."""
+    (0 < rank <= 16: FFM_EPI_RANKOP) and 16-bit storage; tests/test_route_cpu.py pins the regimes of ViT-B/16.
+    targets: which linears carry adapters.  An adapted in-projection / out-projection asks for the FairLoRA word of its
+    product (the qkv forward: FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_LNIN), a tower without MLP sites for the plain words of
+    c_fc / c_proj (no ln_2 fold: the plain GELU product has no folding epilogue), and ln_1's BACKWARD fold stays off for an
+    adapted in-projection: ffm_attention_bwd_lnstat forms the row sums from dqkv alone and would miss the adapter's
+    terms (us A^T gamma, us A^T beta), so ffm_layernorm_bwd runs."""
     w, r = width, rank
     # red_at by row count - measured (one call, alternating): configs[1] (6304 rows) 4.65-4.71 / 4.66-4.67 / 4.75-4.76 ms per
     # step for 0 / 1 / 2; configs[3] (19 700 rows, rank 16: 52 MB of partials per block, whose sum took the attention
@@ -213,17 +230,18 @@ def tower_route(width: int, heads: int, tokens: int, causal: bool, rank: int, dt
         return Route(red_at=red_at)
     tiles = lambda n, k, flags, rk=0: ops.gemm_tiles_n(rows, n, k, flags, rk, dtype, True)
     # ln_1: the c_proj forward leaves the row sums, the qkv product normalises in its epilogue
-    npj = tiles(w, 4 * w, L.EPI_BIAS | L.EPI_LORA | L.EPI_RESIDUAL | L.EPI_RANKOP | L.EPI_ROWSTATS, r)
-    nq = tiles(3 * w, w, L.EPI_BIAS | L.EPI_LNIN)
+    lora, mlp, att = L.EPI_LORA | L.EPI_RANKOP, targets.mlp, targets.attn
+    npj = tiles(w, 4 * w, L.EPI_BIAS | L.EPI_RESIDUAL | L.EPI_ROWSTATS | (lora if mlp else 0), r if mlp else 0)
+    nq = tiles(3 * w, w, L.EPI_BIAS | L.EPI_LNIN | (lora if att else 0), r if att else 0)
     ln1 = npj if (npj > 0 and npj <= 8 and nq > 0) else 0
     # ln_2: row sums from the out-proj forward, the FairLoRA c_fc product with the folding epilogue (its rank operand
     # gamma-scaled), and dA(c_fc) from the raw rows (ffm_lora_grad_partial_ln)
-    npo = tiles(w, w, L.EPI_BIAS | L.EPI_RESIDUAL | L.EPI_ROWSTATS)
-    nf = tiles(4 * w, w, L.EPI_BIAS | L.EPI_LORA | L.EPI_GELU | L.EPI_RANKOP | L.EPI_LNIN, r)
+    npo = tiles(w, w, L.EPI_BIAS | L.EPI_RESIDUAL | L.EPI_ROWSTATS | (lora if att else 0), r if att else 0)
+    nf = tiles(4 * w, w, L.EPI_BIAS | L.EPI_LORA | L.EPI_GELU | L.EPI_RANKOP | L.EPI_LNIN, r) if mlp else 0
     ln2 = npo if (npo > 0 and npo <= 8 and nf > 0 and w % 128 == 0 and r <= 16) else 0
     # FFM_EPI_LGRAD: 0 when the kernel that serves dX(c_proj) has no such epilogue (then the two reduction launches run)
     lgrad = 0
-    if sw.lgrad and packed and r % 4 == 0:
+    if sw.lgrad and packed and r % 4 == 0 and mlp:
         lgrad = max(0, ops.gemm_lgrad_rows(rows, 4 * w, w, r, dtype, True))
         if lgrad > ops.lora_grad_splits(rows):                # (the partial buffers are sized for the reduction kernel's splits)
             lgrad = 0
@@ -237,7 +255,7 @@ def tower_route(width: int, heads: int, tokens: int, causal: bool, rank: int, dt
         ln2_bwd = n1 if (0 < n1 <= 8 and n2 > 0) else 0
     # ln_1's backward: row sums per head from ffm_attention_bwd_lnstat, FFM_EPI_LNB_APPLY on the plain panel tile of dX(qkv)
     ln1_bwd = 0
-    if sw.lnb_fold and sw.lnb_fold1 and ln1 and 2 * heads <= 24 and ops.attention_bwd_lnstat_ok(tokens, causal, dtype):
+    if sw.lnb_fold and sw.lnb_fold1 and ln1 and not att and 2 * heads <= 24 and ops.attention_bwd_lnstat_ok(tokens, causal, dtype):
         if tiles(w, 3 * w, L.EPI_LNB_APPLY) > 0:
             ln1_bwd = 2 * heads
     return Route(ln1, ln2, lgrad, ln2_bwd, ln1_bwd, red_at)
@@ -304,19 +322,26 @@ class _LayerBufs:
     ts1: Optional[Tensor] = None               # operands of the rank > 16 route
     t2: Optional[Tensor] = None
     ts2: Optional[Tensor] = None
+    t3: Optional[Tensor] = None                # ... of attn.in_proj / attn.out_proj (a tower with attention sites)
+    ts3: Optional[Tensor] = None
+    t4: Optional[Tensor] = None
+    ts4: Optional[Tensor] = None
 
 
 class _Stack:
     """A transformer tower (vision with FairLoRA, or text) with its saved activations."""
 
     def __init__(self, width: int, heads: int, layers: int, tokens: int, max_images: int, causal: bool,
-                 rank: int, dtype, device, sw: Switches, x3: bool = False):
+                 rank: int, dtype, device, sw: Switches, x3: bool = False, targets: Targets = Targets()):
         self.width, self.heads, self.layers, self.L = width, heads, layers, tokens
         self.causal, self.rank, self.dtype, self.sw = causal, rank, dtype, sw
+        self.targets = targets if rank else Targets(False, False)
         self.routes: Dict[int, Route] = {}                   # rows -> tower_route (route())
         # x3: float32 tower whose products run on the bf16 matrix cores as hi/lo pairs (FFM_F32_X3)
         # a tower with adapters: (c_fc, c_proj) of every block, made once the frozen weights are loaded (_init_vision_late)
         self.sites: List[Tuple[LoraSite, LoraSite]] = []
+        # ... and (in_proj, out_proj) of every block, where the attention projections carry adapters (Targets.attn)
+        self.asites: List[Tuple[LoraSite, LoraSite]] = []
         # x3 (the text tower, 40 token rows): scratch for the products that are split over K across the grid
         # (ffm_gemm_args.sk_part, csrc/gemm_skinny.hip: N = 512 against K = 1536 / 2048 - c_proj forward, dX(c_fc), dX(qkv));
         # one buffer per tower: its launches are ordered on the tower's stream
@@ -371,26 +396,38 @@ class _Stack:
             self.u = f(T, rank)       # u = g B^T of the rank > 16 route: one for all sites (dead once its us is formed)
             # The LoRA-gradient reductions trail the dX chain on a side stream, so everything they read is kept per layer:
             # gradient of the block output and dL/d(pre) here, the us vectors and the partial sums in the block's sites.
-            self.g_l = [e(T, w) for _ in range(layers)]
-            self.dpre_l = [e(T, 4 * w) for _ in range(layers)]
+            if self.targets.mlp:
+                self.g_l = [e(T, w) for _ in range(layers)]
+                self.dpre_l = [e(T, 4 * w) for _ in range(layers)]
             self.plans = {}                                  # (rows, full backward, block) -> ReducePlan (_reduce_plan)
+        if self.targets.attn:
+            # attention sites: their reductions read the gradient entering the out-projection (dB of out_proj), dqkv (dB of
+            # in_proj) and - where ln_1 is a kernel of its own - its output (dA of in_proj), all three shared or transient in
+            # a tower without them: kept per layer here (o, dA of out_proj's operand, already is).  Nothing of this exists
+            # with the reference's placement.
+            self.g1_l = [e(T, w) for _ in range(layers)]
+            self.dqkv_l = [e(T, 3 * w) for _ in range(layers)]
+            self.h_l = [e(T, w) for _ in range(layers)]
 
     def route(self, rows: int) -> Route:
         """Which fused kernels serve this tower at `rows` rows (decided once per row count, after the weights are loaded)."""
         if rows not in self.routes:
             self.routes[rows] = tower_route(self.width, self.heads, self.L, self.causal, self.rank, self.dtype,
-                                            self.blocks[0].packed is not None, rows, self.sw)
+                                            self.blocks[0].packed is not None, rows, self.sw, targets=self.targets)
         return self.routes[rows]
 
     def layer(self, i: int, rows: int) -> _LayerBufs:
         """Block i's share of the stash (everything the backward pass reads), cut to `rows`."""
         fc, proj = self.sites[i] if self.sites else (None, None)
-        return _LayerBufs(self.x[i][:rows], self.xm[i][:rows], self.qkv[i][:rows], self.o[i][:rows], self.h[:rows],
+        ain, aout = self.asites[i] if self.asites else (None, None)
+        h = self.h_l[i] if self.asites else self.h
+        return _LayerBufs(self.x[i][:rows], self.xm[i][:rows], self.qkv[i][:rows], self.o[i][:rows], h[:rows],
                           self.h2[i][:rows], self.pre[i][:rows], self.act[i][:rows], self.x[i + 1][:rows], self.lse[i],
                           self.st1[i], self.st2[i], self.rowp[i] if self.rowp is not None else None,
                           self.rowp[i + 1] if self.rowp is not None else None,
                           self.rowp2[i] if self.rowp2 is not None else None,
-                          fc and fc.t, fc and fc.ts, proj and proj.t, proj and proj.ts)
+                          fc and fc.t, fc and fc.ts, proj and proj.t, proj and proj.ts,
+                          ain and ain.t, ain and ain.ts, aout and aout.t, aout and aout.ts)
 
 
 class _InferWorkspace:
@@ -443,7 +480,8 @@ class _InferWorkspace:
         rp = self.rowps
         return _LayerBufs(a[:rows], self.xm[:rows], self.qkv[:rows], self.o[:rows], self.h[:rows], self.h2[:rows], None,
                           self.act[:rows], b[:rows], rowp=rp[i & 1] if rp else None, rowp_out=rp[(i + 1) & 1] if rp else None,
-                          rowp2=self.rowp2, t1=self.t, ts1=self.ts, t2=self.t, ts2=self.ts)
+                          rowp2=self.rowp2, t1=self.t, ts1=self.ts, t2=self.t, ts2=self.ts, t3=self.t, ts3=self.ts,
+                          t4=self.t, ts4=self.ts)
 
     def nbytes(self) -> int:
         """Bytes of device memory the workspace holds."""
@@ -594,6 +632,8 @@ class FairLoRAEngine:
         self.side = self._side0 = torch.cuda.Stream(device=self.device)
         self.grad_stream = self._grad0 = torch.cuda.Stream(device=self.device)
         self.ev_layer = [torch.cuda.Event() for _ in range(self._n_layer_events())]
+        if Targets.of(cfg.lora).attn:                 # the attention sites' reductions: one more event per block
+            self.ev_attn = [torch.cuda.Event() for _ in range(self._n_layer_events())]
         self.ev_grads = torch.cuda.Event()
         self.ev_tail = torch.cuda.Event()
         self.ev_tail0 = torch.cuda.Event()
@@ -609,7 +649,8 @@ class FairLoRAEngine:
     # ---------------------------------------------------- vision tower hooks --
     def _init_vision(self, max_images: int) -> None:
         cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
-        self.vis = _Stack(v.width, v.heads, v.layers, v.tokens, max_images, False, cfg.lora.rank, dtype, dev, self.sw)
+        self.vis = _Stack(v.width, v.heads, v.layers, v.tokens, max_images, False, cfg.lora.rank, dtype, dev, self.sw,
+                          targets=Targets.of(cfg.lora))
         P = v.grid * v.grid
         self.cols = torch.zeros(max_images * P, 3 * v.patch * v.patch, device=dev, dtype=dtype)
         self.patch_out = torch.zeros(max_images * P, v.width, device=dev, dtype=dtype)
@@ -635,28 +676,40 @@ class FairLoRAEngine:
         """After the frozen weights are loaded: the tower's LoRA sites and the table that packs their rank operands."""
         cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
         ie = "image_encoder.transformer.resblocks."
-        self.sops = SOperands(self.params, [f"{ie}{i}.mlp.c_{n}." for i in range(v.layers) for n in ("fc", "proj")], cfg, dev)
+        tg = self.vis.targets
+        names = (["attn.in_proj_lora.", "attn.out_proj_lora."] if tg.attn else []) + (["mlp.c_fc.", "mlp.c_proj."] if tg.mlp else [])
+        self.sops = SOperands(self.params, [f"{ie}{i}.{n}" for i in range(v.layers) for n in names], cfg, dev)
         st, w, r, h16, T = self.vis, v.width, cfg.lora.rank, _is16(dtype), self.vis.max_rows
         if not r:
             return
         for i, blk in enumerate(st.blocks):
-            # c_fc has ln_2 folded into it (Route.ln2): its rank operand gamma-scaled too, and - ln_2's backward fold
-            # (Route.ln2_bwd) - the rank operand of dX(c_fc) carries W gamma and W beta + b as rows 14 / 15: its t[14] / t[15]
-            # are the two row sums against those vectors, out of the matrix cores; every consumer masks the slots beyond r
-            fc = LoraSite(self, f"{ie}{i}.mlp.c_fc.", w, 4 * w, T, u=st.u, wide=h16, ln=(blk.ln2_w, blk.ln2_b) if h16 else None,
-                          row1415=(blk.c_fc, blk.d_fc) if (h16 and blk.c_fc is not None and r <= 14) else None)
-            proj = LoraSite(self, f"{ie}{i}.mlp.c_proj.", 4 * w, w, T, u=st.u, wide=h16)
-            st.sites.append((fc, proj))
+            if tg.mlp:
+                # c_fc has ln_2 folded into it (Route.ln2): its rank operand gamma-scaled too, and - ln_2's backward fold
+                # (Route.ln2_bwd) - the rank operand of dX(c_fc) carries W gamma and W beta + b as rows 14 / 15: its t[14] / t[15]
+                # are the two row sums against those vectors, out of the matrix cores; every consumer masks the slots beyond r
+                fc = LoraSite(self, f"{ie}{i}.mlp.c_fc.", w, 4 * w, T, u=st.u, wide=h16, ln=(blk.ln2_w, blk.ln2_b) if h16 else None,
+                              row1415=(blk.c_fc, blk.d_fc) if (h16 and blk.c_fc is not None and r <= 14) else None)
+                proj = LoraSite(self, f"{ie}{i}.mlp.c_proj.", 4 * w, w, T, u=st.u, wide=h16)
+                st.sites.append((fc, proj))
+            if tg.attn:
+                # the in-projection takes ln_1 folded into the qkv product (Route.ln1) as c_fc takes ln_2; ln_1's backward
+                # is never folded for it (tower_route), so its dX product carries no row sums
+                ain = LoraSite(self, f"{ie}{i}.attn.in_proj_lora.", w, 3 * w, T, u=st.u, wide=h16,
+                               ln=(blk.ln1_w, blk.ln1_b) if h16 else None)
+                aout = LoraSite(self, f"{ie}{i}.attn.out_proj_lora.", w, w, T, u=st.u, wide=h16)
+                st.asites.append((ain, aout))
         # dS partials: one size for the tower, the largest of ffm_lora_down's blocks and of the row tiles of either kernel
-        # ffm_gemm_nt may pick for the two dX products (c_proj's carries the dGELU)
-        nb = max([ops.lora_down_blocks_max(T, s.N, r, dtype) for s in (fc, proj)]
-                 + [s.ds_tiles(T, p, dgelu=s is proj) for s in (fc, proj) for p in (False, True)])
-        for s in (s for pair in st.sites for s in pair):
+        # ffm_gemm_nt may pick for the dX products (c_proj's carries the dGELU)
+        last = (st.sites[-1] if tg.mlp else ()) + (st.asites[-1] if tg.attn else ())
+        nb = max([ops.lora_down_blocks_max(T, s.N, r, dtype) for s in last]
+                 + [s.ds_tiles(T, p, dgelu=s.prefix.endswith("mlp.c_proj.")) for s in last for p in (False, True)])
+        for s in (s for pair in st.sites + st.asites for s in pair):
             s.alloc_ds(nb * 8 * r)
         if self.fused_rank:
-            # one table for all blocks, in the order (fc A, proj A, fc B, proj B, fc A with ln_2) per block
+            # one table for all blocks, in the order (fc A, proj A, fc B, proj B, fc A with ln_2) per block; behind them the
+            # attention sites' (in A, out A, in B, out B, in A with ln_1) per block
             ent = []
-            for fc, proj in st.sites:
+            for fc, proj in st.sites + st.asites:
                 (fa, fb, *fln), (pa, pb) = fc.pack_entries(), proj.pack_entries()
                 ent += [fa, pa, fb, pb, *fln]
             self.pack_plan = ops.PackPlan(ent, dtype, dev)
@@ -792,7 +845,30 @@ class FairLoRAEngine:
         for i, blk in enumerate(st.blocks):
             lb = bufs.layer(i, rows)
             x, xm, qkv, o, h, h2, act = lb.x, lb.xm, lb.qkv, lb.o, lb.h, lb.h2, lb.act
-            if fold:
+            if st.asites:
+                # adapters on the attention projections: the packed in-projection (before q is scaled: the attention
+                # kernels scale) and the out-projection, a c_proj-type product with the residual (and ln_2's row sums)
+                ain, aout = st.asites[i]
+                if self.fused_rank:
+                    ro = ain.rank_fwd(attr, rows_per_sample, lb.t3, lb.ts3, ln=bool(fold))
+                    if fold:
+                        ln = ops.LnIn(lb.rowp, 1 if i == 0 else fold, blk.c_in, lb.st1[0], lb.st1[1], rk=ain.lnrk)
+                        gemm(x, blk.w_in_ln, qkv, bias=blk.d_in, lw=ain.B, rankop=ro, b_packed=blk.pk("w_in_ln"), ln_in=ln)
+                    else:
+                        ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
+                        gemm(h, blk.w_in, qkv, bias=blk.b_in, lw=ain.B, rankop=ro, b_packed=blk.pk("w_in"))
+                else:
+                    ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
+                    ain.down_fwd(h, attr, rows_per_sample, lb.t3, lb.ts3)
+                    gemm(h, blk.w_in, qkv, bias=blk.b_in, ts=lb.ts3, lw=ain.B)
+                ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
+                if self.fused_rank:
+                    gemm(o, blk.w_out, xm, bias=blk.b_out, lw=aout.B, res=x, b_packed=blk.pk("w_out"),
+                         rankop=aout.rank_fwd(attr, rows_per_sample, lb.t4, lb.ts4), rowstats=lb.rowp2 if fold2 else None)
+                else:
+                    aout.down_fwd(o, attr, rows_per_sample, lb.t4, lb.ts4)
+                    gemm(o, blk.w_out, xm, bias=blk.b_out, ts=lb.ts4, lw=aout.B, res=x)
+            elif fold:
                 # ln_1 rides inside the qkv product: raw rows x gamma-scaled weight, normalised in the epilogue with the
                 # row sums the producer of x left behind (block 0: embed_lnpre, else the previous block's c_proj)
                 ln = ops.LnIn(lb.rowp, 1 if i == 0 else fold, blk.c_in, lb.st1[0], lb.st1[1])
@@ -800,10 +876,12 @@ class FairLoRAEngine:
             else:
                 ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
                 gemm(h, blk.w_in, qkv, bias=blk.b_in, b_packed=blk.pk("w_in"))
-            ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
-            gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=lb.rowp2 if fold2 else None)
+            if not st.asites:
+                ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
+                gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=lb.rowp2 if fold2 else None)
             if not fold2:
                 ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, lb.st2[0], lb.st2[1])
+            r = st.rank if st.sites else 0            # (a tower with attention sites alone: plain c_fc / c_proj)
             sfc, sproj = st.sites[i] if r else (None, None)
             if r and self.fused_rank:
                 ro = sfc.rank_fwd(attr, rows_per_sample, lb.t1, lb.ts1, ln=bool(fold2))
@@ -822,8 +900,9 @@ class FairLoRAEngine:
                 sproj.down_fwd(act, attr, rows_per_sample, lb.t2, lb.ts2)
                 gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, ts=lb.ts2, lw=sproj.B, res=xm)
             else:
-                fc(h2, blk.w_fc, bias=blk.b_fc)
-                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, res=xm)
+                fc(h2, blk.w_fc, bias=blk.b_fc, b_packed=blk.pk("w_fc"))
+                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, res=xm, b_packed=blk.pk("w_proj"),
+                     rowstats=lb.rowp_out if (fold and i + 1 < st.layers) else None)
             out = lb.x_out
         return out
 
@@ -832,7 +911,8 @@ class FairLoRAEngine:
         """st.g[:rows] holds dL/d(tower output) (a FairLoRA tower with grad_in_last: st.g_l[layers - 1] does - the buffer the
         last block's reductions read - and no copy is made); on return st.g holds dL/d(tower input) (if need_input_grad).
         LoRA gradients are written into params.grad."""
-        r = st.rank
+        r = st.rank if st.sites else 0                # (attention sites alone: the MLP's backward is the plain one)
+        att = bool(st.asites)
         gemm = st.gemm
         g, g1 = st.g[:rows], st.g1[:rows]
         main = torch.cuda.current_stream(self.device)
@@ -841,7 +921,12 @@ class FairLoRAEngine:
             blk = st.blocks[i]
             x, xm = st.x[i][:rows], st.xm[i][:rows]
             pre, act, h2 = st.pre[i][:rows], st.act[i][:rows], st.h2[i][:rows]
-            last = (i == 0) and not need_input_grad
+            # the dX chain ends inside block 0: behind dX(c_proj) - or, with attention sites, behind the attention backward
+            # (last_att: block 0 runs its MLP part as every other block does and stops at dqkv)
+            last_att = att and (i == 0) and not need_input_grad
+            last = (i == 0) and not need_input_grad and not att
+            if att:
+                g1 = st.g1_l[i][:rows]                # dL/d x_mid, kept per layer: dB(out_proj) reads it on the side stream
             if r:
                 # gradient w.r.t. this block's output lives in its own buffer (read later by the side stream)
                 gi, dpre = st.g_l[i][:rows], st.dpre_l[i][:rows]
@@ -909,7 +994,7 @@ class FairLoRAEngine:
                         # this block's six gradient tensors are complete: sum their partials now, behind the four reductions
                         # on the same side stream (one launch per block; only block 0's is left when the dX chain ends -
                         # ONE launch for all 72 tensors at the end sat in the step's tail for ~50 us)
-                        self._reduce_plan(st, rows, need_input_grad, i).run()
+                        self._reduce_plan(st, rows, need_input_grad or att, i).run()
                 # red_at: where the side stream may start them (everything they read is kept per layer).  0: behind this
                 # block's dX(c_fc) - beside its LayerNorm / out-proj / attention backward; 1: behind its attention backward;
                 # 2: behind the whole block - beside the NEXT block's two FairLoRA products, whose main loops live on
@@ -929,6 +1014,11 @@ class FairLoRAEngine:
                 gemm(dpre, blk.w_fc_t, st.dh[:rows])
             if not lnb:
                 ops.layernorm_bwd(st.dh[:rows], xm, blk.ln2_w, st.st2[i][0], st.st2[i][1], gi, g1)
+            if att:
+                self._attn_sites_backward(st, i, rows, images, attr, rows_per_sample, g1, gout, last_att, red_at, reductions if r else None)
+                if last_att:
+                    break
+                continue
             gemm(g1, blk.w_out_t, st.do[:rows], b_packed=blk.pk("w_out_t"))
             # ln_1's backward: its two row sums leave with the attention backward (two partial rows per head), and the dX
             # product of the in-projection stores dL/d x = LayerNorm backward(g_h) + g1 directly
@@ -946,12 +1036,66 @@ class FairLoRAEngine:
                 ops.layernorm_bwd(st.dh[:rows], x, blk.ln1_w, st.st1[i][0], st.st1[i][1], g1, gout)
             if red_at == 2:
                 reductions()
-        if r:
+        if r or att:
             if self.sops.glob:
                 self._glue(self.sops.finish, self.grad_stream)     # dS_eff -> dS, dS_global
             self._ev_record(self.ev_grads, self.grad_stream)
             self._ev_wait(main, self.ev_grads)
         return g
+
+    def _attn_sites_backward(self, st: _Stack, i: int, rows: int, images: int, attr: Optional[Tensor], rps: int,
+                             g1: Tensor, gout: Tensor, last: bool, red_at: int, mlp_reductions) -> None:
+        """Block i's attention part of the backward pass where attn.in_proj / attn.out_proj carry adapters: dX(out_proj)
+        with the adapter's dx term, the attention backward, dX(in_proj) likewise and ln_1's backward as its own kernel
+        (tower_route keeps ln_1's backward fold off here).  last: the chain ends at dqkv - the in-projection takes the
+        stand-alone down projection for us and the dS partials, as block 0's c_fc does in a tower without these sites.
+        Everything the four reductions read is the block's own (g1_l, dqkv_l, o, h_l or the raw rows x; us and the partials
+        in the sites), so they trail the chain on the side stream behind one event and no buffer waits for them."""
+        blk, gemm, main = st.blocks[i], st.gemm, torch.cuda.current_stream(self.device)
+        ain, aout = st.asites[i]
+        x, o, dqkv, do, dh = st.x[i][:rows], st.o[i][:rows], st.dqkv_l[i][:rows], st.do[:rows], st.dh[:rows]
+        rt = st.route(rows)
+        if self.fused_rank:
+            gemm(g1, blk.w_out_t, do, lw=aout.A, lw_is_kr=True, rankop=aout.rank_bwd(attr, rps, rows), b_packed=blk.pk("w_out_t"))
+        else:
+            aout.down_bwd(g1, attr, rps)
+            gemm(g1, blk.w_out_t, do, ts=aout.us[:rows], lw=aout.A, lw_is_kr=True)
+        ops.attention_bwd(st.qkv[i][:rows], o, do, st.lse[i], st.delta, dqkv, images, st.L, st.heads, st.causal)
+        if red_at == 1 and mlp_reductions is not None:
+            mlp_reductions()
+        if last or not self.fused_rank:
+            ain.down_bwd(dqkv, attr, rps)
+        if not last:
+            if self.fused_rank:
+                gemm(dqkv, blk.w_in_t, dh, lw=ain.A, lw_is_kr=True, rankop=ain.rank_bwd(attr, rps, rows), b_packed=blk.pk("w_in_t"))
+            else:
+                gemm(dqkv, blk.w_in_t, dh, ts=ain.us[:rows], lw=ain.A, lw_is_kr=True)
+            ops.layernorm_bwd(dh, x, blk.ln1_w, st.st1[i][0], st.st1[i][1], g1, gout)
+        if red_at == 2 and mlp_reductions is not None:
+            mlp_reductions()
+        ev = self.ev_attn[i]
+        self._ev_record(ev, main)
+        self._ev_wait(self.grad_stream, ev)
+        with self._on(self.grad_stream):
+            aout.grad_B(g1)
+            aout.grad_A(o)
+            ain.grad_B(dqkv)
+            if rt.ln1:
+                ain.grad_A(x, ln_stats=st.st1[i])         # ln_1 was folded into the qkv product: dA from the raw rows
+            else:
+                ain.grad_A(st.h_l[i][:rows])
+            self._attn_reduce_plan(st, rows, not last, i).run()
+
+    def _attn_reduce_plan(self, st: _Stack, rows: int, in_gemm: bool, layer: int):
+        """As _reduce_plan, for the block's attention sites.  in_gemm: dX(in_proj) ran and left the in-projection's dS
+        partials (False: the stand-alone down projection did)."""
+        key = (rows, in_gemm, layer, "attn")
+        if key not in st.plans:
+            (ain, aout), pk = st.asites[layer], st.blocks[layer].packed is not None
+            ob, oa, os_ = aout.reduce_entries(rows, aout.ds_rows(rows, pk))
+            ib, ia, is_ = ain.reduce_entries(rows, ain.ds_rows(rows, pk, gemm=in_gemm))
+            st.plans[key] = ops.ReducePlan([os_, is_, ob, oa, ib, ia], self.device)
+        return st.plans[key]
 
     def _reduce_plan(self, st: _Stack, rows: int, full_bwd: bool, layer: int):
         """Descriptor table (built once per row count and block) that sums the block's partials into params.grad."""
@@ -1170,7 +1314,7 @@ class FairLoRAEngine:
         a32 = self.attr_i32[:b] if has_attr else None
         ops.gemm_nt(self.dfeat[:rows], self.proj, self.vis.dh[:rows], b_packed=self.pk_out.get("proj"))
         # (straight into the buffer the last block's LoRA-gradient reductions read: no copy on the main stream)
-        gl = self.vis.rank > 0
+        gl = bool(self.vis.sites)
         ops.layernorm_bwd(self.vis.dh[:rows], self.vis.x[v.layers][:rows], self.lnpost[0], self.post_stats[0],
                           self.post_stats[1], None, (self.vis.g_l[v.layers - 1] if gl else self.vis.g)[:rows])
         self._stack_backward(self.vis, rows, images, a32, L * S, self.is3d, grad_in_last=gl)

@@ -71,6 +71,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--lora_local_s", type=bool, default=False)
     a("--shared_half_s", type=bool, default=False)
     a("--lora_global_s", type=bool, default=False)
+    a("--lora_targets", type=str, default="mlp", choices=list(C.LORA_TARGETS),
+      help="TRAINER.GLP_OT_LORA.TARGETS: which linears of a ViT block carry the adapters - mlp (the reference), attn (the "
+           "attention's in-projection and out-projection) or mlp+attn; an extension beyond the reference")
     a("--lambda_fairness", type=float, default=0.0)
     a("--fairness_grad", action="store_true",
       help="let the --lambda_fairness term reach the gradients (an extension: the reference detaches it, which is the default)")
@@ -153,7 +156,8 @@ def setup_cfg(args) -> NS:
                    GLP_OT_LORA=NS(UNFREEZE_IMAGE_ENCODER=args.unfreeze_image_encoder,
                                   UNFREEZE_TEXT_ENCODER=args.unfreeze_text_encoder, RANK=args.lora_rank,
                                   ALPHA=args.lora_alpha, TYPE=args.lora_type, LOCAL_S=args.lora_local_s,
-                                  GLOBAL_S=args.lora_global_s, DISABLE_ATTR=args.disable_attr)),
+                                  GLOBAL_S=args.lora_global_s, DISABLE_ATTR=args.disable_attr,
+                                  TARGETS=args.lora_targets)),
     )
     for path in (args.dataset_config_file, args.config_file):
         if path:
@@ -221,7 +225,8 @@ def main(argv: Optional[List[str]] = None, log=print, cfg_hook=None):
             from .clip_adapter import vision_for_input
             vision = vision_for_input(cfg, vision)
         mcfg = C.ModelCfg(vision=vision, text=base.text, lora=C.LoraCfg(rank=args.lora_rank, alpha=args.lora_alpha,
-                                                                            num_groups=G),
+                                                                            num_groups=G,
+                                                                            targets=cfg.TRAINER.GLP_OT_LORA.TARGETS),
                           n_prompts=args.num_prompt, n_ctx=args.n_ctx,
                           dim_per_3d_slice=args.dim_per_3d_slice if is3d else 0)
         cfg.DATASET.ATTRIBUTES = [args.attribute_type]

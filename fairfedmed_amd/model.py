@@ -350,13 +350,20 @@ class SVLoRALinear(nn.Module):
 
 
 def apply_lora_to_model(model: nn.Module, unfreeze_image_encoder: bool, rank: int = 4, alpha: float = 0.04,
-                        lora_type: str = "FairLoRA", global_s: bool = False, num_attrs: int = 1) -> None:
+                        lora_type: str = "FairLoRA", global_s: bool = False, num_attrs: int = 1,
+                        targets: str = "mlp") -> None:
     """The reference's injection rules (trainers/GLP_OT_SVLoRA.py:503-573) for modules under 'image_encoder.':
     ViT - every nn.Linear whose name contains '.mlp.' becomes a FairLoRALinear; ResNet - every 1x1 nn.Conv2d named
     '*conv*' under 'layer*' becomes a FairLoRALinear (downsample.0 is not named conv and stays), every nn.Linear
-    of 'attnpool' a plain LoRALinear."""
+    of 'attnpool' a plain LoRALinear.
+    targets (an extension, config.LoraCfg.targets): 'mlp' is the reference's rule; 'attn' / 'mlp+attn' put adapters on the
+    attention's packed in-projection and its out-projection, which exist in the engine-backed CustomCLIP only (a module
+    tree's nn.MultiheadAttention has no nn.Linear for the packed projection to wrap)."""
     if lora_type not in ("LoRA", "SVLoRA", "FairLoRA"):
         raise NotImplementedError(lora_type)
+    from .config import LORA_TARGETS
+    if targets not in LORA_TARGETS:
+        raise ValueError(f"targets must be one of {LORA_TARGETS}, got {targets!r}")
     if isinstance(model, CustomCLIP):
         # the engine-backed CustomCLIP carries its adapters from construction (its image encoder is a sequence of HIP
         # launches, not nn.Linear modules to wrap): the reference's call sequence CustomCLIP(...) ->
@@ -365,12 +372,18 @@ def apply_lora_to_model(model: nn.Module, unfreeze_image_encoder: bool, rank: in
         want = (int(rank), float(alpha), lora_type, bool(global_s) and lora_type != "LoRA",
                 int(num_attrs) if lora_type == "FairLoRA" else 1)
         have = (lo.rank, float(lo.alpha), lo.lora_type, bool(lo.global_s), lo.num_groups)
+        if targets != lo.targets:
+            raise ValueError(f"apply_lora_to_model asks for targets {targets!r}, the model was built with {lo.targets!r}: "
+                             f"set cfg.TRAINER.GLP_OT_LORA.TARGETS accordingly")
         if not unfreeze_image_encoder:
             raise NotImplementedError("unfreeze_image_encoder=False: the engine always carries the adapters")
         if want != have:
             raise ValueError(f"apply_lora_to_model asks for (rank, alpha, type, global_s, groups) = {want}, the model "
                              f"was built with {have}: set cfg.TRAINER.GLP_OT_LORA accordingly")
         return
+    if targets != "mlp":
+        raise NotImplementedError(f"targets {targets!r}: adapters on the attention projections exist in the engine-backed "
+                                  f"CustomCLIP only")
     for name, module in dict(model.named_modules()).items():
         if not (unfreeze_image_encoder and name.startswith("image_encoder.")):
             continue

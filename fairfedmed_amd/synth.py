@@ -36,9 +36,13 @@ def manifest(cfg: ModelCfg) -> "OrderedDict[str, Tuple[int, ...]]":
     m["prompt_learner.token_suffix"] = (nrow, t.context_length - 1 - cfg.n_ctx, t.width)
     ie = "image_encoder."
     if isinstance(v, ResNetCfg):
+        if lo.targets != "mlp":
+            # (the attention pool already carries the reference's plain LoRA, trainers/GLP_OT_SVLoRA.py:541-573)
+            raise NotImplementedError(f"lora targets {lo.targets!r}: the RN50 tower has the reference's placement only")
         _manifest_resnet(m, cfg)
         _manifest_text(m, cfg)
         return m
+    on_mlp, on_attn = lo.on_mlp, lo.on_attn
     m[ie + "class_embedding"] = (v.width,)
     m[ie + "positional_embedding"] = (v.tokens, v.width)
     m[ie + "proj"] = (v.width, v.out_dim)
@@ -51,15 +55,24 @@ def manifest(cfg: ModelCfg) -> "OrderedDict[str, Tuple[int, ...]]":
         m[p + "attn.in_proj_bias"] = (3 * v.width,)
         m[p + "attn.out_proj.weight"] = (v.width, v.width)
         m[p + "attn.out_proj.bias"] = (v.width,)
+        if on_attn:
+            # LoraCfg.targets with 'attn' (an extension): adapters on the packed in-projection and on the out-projection.
+            # The frozen keys above keep their names; the adapters' own sit behind them
+            for name, fout in (("in_proj_lora", 3 * v.width), ("out_proj_lora", v.width)):
+                q = f"{p}attn.{name}."
+                m[q + "lora_A.weight"] = (v.width, lo.rank)
+                _manifest_s(m, q, lo)
+                m[q + "lora_B.weight"] = (lo.rank, fout)
         m[p + "ln_1.weight"] = (v.width,)
         m[p + "ln_1.bias"] = (v.width,)
         for name, fin, fout in (("c_fc", v.width, 4 * v.width), ("c_proj", 4 * v.width, v.width)):
             q = f"{p}mlp.{name}."
             m[q + "original_linear.weight"] = (fout, fin)
             m[q + "original_linear.bias"] = (fout,)
-            m[q + "lora_A.weight"] = (fin, lo.rank)
-            _manifest_s(m, q, lo)
-            m[q + "lora_B.weight"] = (lo.rank, fout)
+            if on_mlp:
+                m[q + "lora_A.weight"] = (fin, lo.rank)
+                _manifest_s(m, q, lo)
+                m[q + "lora_B.weight"] = (lo.rank, fout)
         m[p + "ln_2.weight"] = (v.width,)
         m[p + "ln_2.bias"] = (v.width,)
     m[ie + "ln_post.weight"] = (v.width,)

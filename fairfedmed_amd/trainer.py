@@ -208,7 +208,8 @@ class GLP_OT_SVLoRA:
             vision = vision_for_input(cfg, vision)
         return C.ModelCfg(vision=vision, text=base.text,
                           lora=C.LoraCfg(rank=lora.RANK, alpha=lora.ALPHA, num_groups=G, lora_type=lora.TYPE,
-                                         global_s=bool(getattr(lora, "GLOBAL_S", False))),
+                                         global_s=bool(getattr(lora, "GLOBAL_S", False)),
+                                         targets=str(getattr(lora, "TARGETS", "mlp"))),
                           n_prompts=cfg.TRAINER.GLP_OT.N, n_ctx=cfg.TRAINER.GLP_OT.N_CTX, n_cls=len(names), eot=eot,
                           pixel_mean=tuple(cfg.INPUT.PIXEL_MEAN), pixel_std=tuple(cfg.INPUT.PIXEL_STD),
                           dim_per_3d_slice=cfg.DATASET.DIM_PER_3D_SLICE if is_3d else 0,

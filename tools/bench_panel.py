@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Panel GEMM (csrc/gemm_panel_impl.h) vs the 128x128 kernel on the eight GEMMs of a vision block (bs 32):
-us / TFLOP/s per shape with the engine's epilogues."""
+us / TFLOP/s per shape with the engine's epilogues.
+--attn: the two adapted products of LoraCfg.targets 'attn' instead - the qkv forward with its adapter (the word
+FFM_EPI_BIAS | FFM_EPI_LORA) and the same with ln_1 folded in (| FFM_EPI_LNIN: a panel epilogue only, so its yardstick is
+the 128x128 kernel's launch WITHOUT the fold, which still needs ffm_layernorm_fwd in front of it) - and the adapted out-proj.
+(The word without the fold lost its run and has no panel kernel any more: its two columns are both the 128x128 kernel.)"""
 import os
 import sys
 
@@ -55,6 +59,12 @@ def case(name, N, K, mode):
                   lw_is_kr=kr, rankop=ro)
     bp = ops.pack_b(b)
     u0 = bench(lambda: ops.gemm_nt(a, b, out, **kw))
+    if "n" in mode:
+        # ln folded in (panel only): partial row sums of a unit-variance row, the weight's row sums, the rank corrections
+        part = torch.zeros(M, 2, device="cuda")
+        part[:, 1] = K
+        kw["ln_in"] = ops.LnIn(part, 1, b.float().sum(1).contiguous(), torch.empty(M, device="cuda"), torch.empty(M, device="cuda"),
+                               rk=torch.zeros(32, device="cuda") if "l" in mode else None)
     u1 = bench(lambda: ops.gemm_nt(a, b, out, b_packed=bp, **kw))
     fl = 2.0 * M * N * K
     print(f"{name:10s} N{N:5d} K{K:5d} [{mode:5s}] 128x128 {u0:6.1f} us {fl / u0 / 1e6:7.1f} TF/s | panel {u1:6.1f} us "
@@ -64,9 +74,13 @@ def case(name, N, K, mode):
 
 if __name__ == "__main__":
     tot = [0.0, 0.0]
-    for name, N, K, mode in [("qkv fwd", 3 * W, W, "b"), ("out fwd", W, W, "br"), ("fc fwd", 4 * W, W, "blg"),
-                             ("proj fwd", W, 4 * W, "blr"), ("proj dX", 4 * W, W, "lkd"), ("fc dX", W, 4 * W, "lk"),
-                             ("out dX", W, W, ""), ("qkv dX", W, 3 * W, "")]:
+    cases = [("qkv fwd", 3 * W, W, "b"), ("out fwd", W, W, "br"), ("fc fwd", 4 * W, W, "blg"),
+             ("proj fwd", W, 4 * W, "blr"), ("proj dX", 4 * W, W, "lkd"), ("fc dX", W, 4 * W, "lk"),
+             ("out dX", W, W, ""), ("qkv dX", W, 3 * W, "")]
+    if "--attn" in sys.argv:
+        cases = [("qkv fwd", 3 * W, W, "b"), ("qkv+lora", 3 * W, W, "bl"), ("qkv+lora+ln", 3 * W, W, "bln"),
+                 ("out+lora", W, W, "blr"), ("out+lora dX", W, W, "lk"), ("qkv+lora dX", W, 3 * W, "lk")]
+    for name, N, K, mode in cases:
         u = case(name, N, K, mode)
         tot[0] += u[0]
         tot[1] += u[1]
