@@ -144,6 +144,11 @@ SIGNATURES = {
     "ffm_scale_by": [_vp, _vp, _vp, _i64, _vp],
     "ffm_scale_acc": [_vp, _vp, _vp, _i64, _vp],
     "ffm_fedavg_finish": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp],
+    "ffm_dp_norm_ws_bytes": [_i64],
+    "ffm_dp_norm": [_vp, _vp, _i64, _vp, _vp],
+    "ffm_dp_privatise": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _i64, _i32, _i32, _i32, _vp, _vp],
+    "ffm_dp_noise": [_vp, _i64, _f32, _i64, _i32, _i32, _vp],
+    "ffm_dp_philox": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp],
     "ffm_cast_f32_to": [_vp, _vp, _i64, _i32, _vp],
     "ffm_cast_to_f32": [_vp, _vp, _i64, _i32, _vp],
     "ffm_transpose_cast": [_vp, _vp, _i32, _i32, _i32, _vp],

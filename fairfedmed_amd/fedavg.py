@@ -24,6 +24,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from . import dp as D
+
 Tensor = torch.Tensor
 
 
@@ -67,11 +69,23 @@ class FedAvgAggregator:
     and ``bench.py --gpus N`` go through here, so the bench times the product's round boundary.  On a GPU every pass is a
     HIP kernel (ffm_scale_by / ffm_scale_acc / ffm_fedavg_finish) over device-resident weight vectors that are built once
     per (client, participants) and cached; on the CPU (BASELINE.json configs[0]: gloo plumbing) the same passes are host
-    tensor arithmetic."""
+    tensor arithmetic.
+
+    ``dp`` (a ``dp.DPCfg``; off by default, and then nothing here changes): client-level differential privacy, DESIGN.md
+    section 4.18.  ``begin(round=t)`` names the round; ``add`` then clips the client's update against ``global_prev`` and adds
+    its noise share (ffm_dp_norm + ffm_dp_privatise in place of ffm_scale_by / ffm_scale_acc; on the CPU ``dp.privatise``);
+    ``finish`` is the same post-processing.  ``dp_stats`` afterwards: {client: (norm, clip factor)} of this rank's clients."""
 
     def __init__(self, flat: Tensor, offsets: Dict[str, Tuple[int, Tuple[int, ...]]], num_groups: int, rank_dim: int,
-                 shared_half_s: bool = True, beta: float = 0.999, group=None, wcache_entries: int = 64):
+                 shared_half_s: bool = True, beta: float = 0.999, group=None, wcache_entries: int = 64, *,
+                 dp: Optional[D.DPCfg] = None):
         self.flat, self.offsets = flat, offsets
+        self.dp, self._round = dp, None
+        self._dp_clients: List[int] = []                   # this round's clients, in the order of their rows of _dp_dev
+        self._dp_host: Dict[int, Tuple[float, float]] = {}
+        self._dp_dev: Optional[Tensor] = None              # GPU: fp32 [clients, 2] = {norm, clip factor}, read on demand
+        self._dp_scratch: Optional[Tensor] = None
+        self._wmax: "Dict[tuple, float]" = {}
         self.G, self.r = num_groups, rank_dim
         self.shared_half_s, self.beta, self.group = shared_half_s, beta, group
         self.global_prev = flat.detach().clone()            # w_g: the global weights before round 0
@@ -98,15 +112,70 @@ class FedAvgAggregator:
         return w
 
     @torch.no_grad()
-    def begin(self) -> None:
+    def begin(self, round: Optional[int] = None) -> None:
+        """``round``: the round's number t, which (with the client) names the noise stream; needed with ``dp`` only."""
         self._added, self._grouped = 0, False
+        if self.dp is not None:
+            if round is None:
+                raise ValueError("FedAvgAggregator(dp=...): begin(round=t) must name the round (it selects the noise stream)")
+            self._round, self._dp_clients, self._dp_host = int(round), [], {}
+
+    def _sigma(self, participants: Sequence[int], n_client: Sequence[int],
+               n_client_by_attr: Optional[Sequence[Sequence[int]]]) -> float:
+        if self.dp.noise_multiplier == 0:
+            return 0.0
+        key = (tuple(participants), tuple(n_client),
+               None if n_client_by_attr is None else tuple(map(tuple, n_client_by_attr)))
+        wm = self._wmax.get(key)
+        if wm is None:
+            if len(self._wmax) >= self._wcache_entries:
+                self._wmax.pop(next(iter(self._wmax)))
+            wm = self._wmax[key] = D.weight_max(participants, n_client, n_client_by_attr, self.s_offsets.numel() > 0)
+        return D.sigma(self.dp, len(participants), wm)
+
+    def _add_private(self, src: Tensor, w: Tensor, client: int, sigma: float) -> None:
+        """buf (+)= c_client: the clipped, weighted, noised contribution."""
+        cfg, row = self.dp, len(self._dp_clients)
+        if src.is_cuda:
+            from . import ops
+            if self._dp_scratch is None:
+                self._dp_scratch = ops.dp_scratch(src.numel(), src.device)
+            if self._dp_dev is None or self._dp_dev.shape[0] <= row:
+                grown = torch.zeros(max(8, 2 * (row + 1)), 2, dtype=torch.float32, device=src.device)
+                if self._dp_dev is not None:
+                    grown[:self._dp_dev.shape[0]] = self._dp_dev
+                self._dp_dev = grown
+            ops.dp_norm(src, self.global_prev, self._dp_scratch)
+            ops.dp_privatise(src, self.global_prev, w, self.buf, self._dp_scratch, cfg.clip, sigma, cfg.seed, self._round,
+                             client, accumulate=self._added > 0, stats=self._dp_dev[row])
+        else:
+            c, nu, s = D.privatise(src, self.global_prev, w, cfg.clip, sigma, cfg.seed, self._round, client)
+            if self._added == 0:
+                self.buf.copy_(c)
+            else:
+                self.buf.add_(c)
+            self._dp_host[client] = (nu, s)
+        self._dp_clients.append(client)
+
+    @property
+    def dp_stats(self) -> Dict[int, Tuple[float, float]]:
+        """{client: (norm of its update, clip factor applied)} for the clients this rank added since ``begin``.  On a GPU
+        this read is the one synchronisation that ``dp`` adds to a round."""
+        if self._dp_dev is not None and len(self._dp_host) != len(self._dp_clients):
+            rows = self._dp_dev[:len(self._dp_clients)].cpu().tolist()
+            self._dp_host = {c: (r[0], r[1]) for c, r in zip(self._dp_clients, rows)}
+        return dict(self._dp_host)
 
     @torch.no_grad()
     def add(self, src: Tensor, client: int, participants: Sequence[int], n_client: Sequence[int],
             n_client_by_attr: Optional[Sequence[Sequence[int]]] = None) -> None:
         """buf (+)= w_client (.) src: this rank's share of sum_k w_k theta_k (utils/fed_utils.py:76-86)."""
         w = self._weights(client, participants, n_client, n_client_by_attr)
-        if src.is_cuda:
+        if self.dp is not None:
+            if self._round is None:
+                raise ValueError("FedAvgAggregator(dp=...): begin(round=t) must come before add")
+            self._add_private(src, w, client, self._sigma(participants, n_client, n_client_by_attr))
+        elif src.is_cuda:
             from . import ops
             (ops.scale_by if self._added == 0 else ops.scale_acc)(src, w, self.buf)
         elif self._added == 0:
@@ -147,7 +216,7 @@ class FedAvgAggregator:
                   n_client_by_attr: Optional[Sequence[Sequence[int]]], epoch: int, max_epoch: int) -> Tensor:
         """One client per rank: all ranks call this at the round boundary; afterwards `flat` holds the new global
         weights on every rank."""
-        self.begin()
+        self.begin(round=epoch)
         self.add(self.flat, client, participants, n_client, n_client_by_attr)
         self.flat.copy_(self.finish(epoch, max_epoch, grouped=n_client_by_attr is not None))
         return self.flat

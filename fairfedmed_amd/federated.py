@@ -47,6 +47,44 @@ class FedArgs:
     # optimizer state is handed on after each: no concurrency, for parity runs); False gives every rank its own
     # optimizer state (clients of a round train concurrently: the throughput mode).
     compat_sequential_optimizer: bool = False
+    # Client-level differential privacy at the round boundary (dp.py; an extension beyond the
+    # reference).  dp_clip: the L2 bound C on one client's update over the flat trainable buffer, 0 = off; dp_noise: the
+    # noise multiplier z (0 clips only); dp_seed: key of the noise generator (default: `seed`, else 0); dp_delta: the
+    # delta the logged epsilon is stated for.
+    dp_clip: float = 0.0
+    dp_noise: float = 0.0
+    dp_seed: Optional[int] = None
+    dp_delta: float = 1e-5
+
+
+def dp_config(args: FedArgs, trainer=None):
+    """The DPCfg of a run, or None with --dp_clip 0.  Refuses an engine with BatchNorm buffers: their running statistics
+    are a second quantity every client releases, and nothing clips or noises it."""
+    if not args.dp_clip:
+        return None
+    from .dp import DPCfg
+    if args.dp_clip < 0:
+        raise ValueError(f"dp_clip must be positive (0 = off), got {args.dp_clip}")
+    eng = getattr(trainer, "engine", None)
+    if trainer is not None and (eng is None or not hasattr(eng, "params")):
+        raise ValueError("dp_clip > 0 needs a trainer whose engine keeps its trainable tensors in one flat buffer")
+    if eng is not None and hasattr(eng, "buffers_flat"):
+        raise ValueError("dp_clip > 0 with an engine that has BatchNorm buffers (the RN50 tower): the running statistics "
+                         "are averaged over the clients as a second released quantity with no clip and no noise on it, so "
+                         "the privacy bound would not hold; use a ViT tower or run without dp_clip")
+    seed = args.dp_seed if args.dp_seed is not None else (args.seed if args.seed is not None else 0)
+    return DPCfg(clip=args.dp_clip, noise_multiplier=args.dp_noise, seed=int(seed), delta=args.dp_delta)
+
+
+def _dp_log(hist, dp, stats: Dict[int, tuple], epoch: int, log) -> None:
+    """One round's {client: (norm, clip factor)} into the history, with the bound on epsilon after epoch + 1 rounds."""
+    from .dp import epsilon
+    norms = {c: stats[c][0] for c in sorted(stats)}
+    hist.setdefault("dp_norms", []).append(norms)
+    hist.setdefault("dp_epsilon", []).append(epsilon(dp.noise_multiplier, epoch + 1, dp.delta))
+    clipped = [c for c in norms if stats[c][1] < 1.0]
+    log(f"round {epoch}: dp update norms " + " ".join(f"{c}:{v:.4g}" for c, v in norms.items())
+        + f"  clipped at {dp.clip:g}: {clipped}  epsilon <= {hist['dp_epsilon'][-1]:.4g} (delta {dp.delta:g})")
 
 
 def average_weights_ema(w_g: Dict[str, Tensor], w: Dict[int, Dict[str, Tensor]], idxs_users: Sequence[int],
@@ -134,13 +172,18 @@ def _counts(trainer, attribute: str, n_users: int):
 
 def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=print) -> Dict[str, list]:
     """One process, one GPU: the reference's round loop verbatim in structure.  Returns the per-round means of
-    [accuracy, error_rate, macro_f1, auc] over the tested clients, and the final per-client weights."""
+    [accuracy, error_rate, macro_f1, auc] over the tested clients, and the final per-client weights.
+
+    With ``args.dp_clip > 0`` the round's average is formed by ``fedavg.FedAvgAggregator(dp=...)`` over the engine's flat
+    trainable buffer instead of ``average_weights_ema``: the clip bounds ONE vector per client and the
+    noise is indexed by the flat position, exactly as under ``run_fedotplora_ranks``, so the two drivers agree."""
     cfg = trainer.cfg
     users = cfg.DATASET.USERS if hasattr(cfg.DATASET, "USERS") else args.num_users
     attribute = attribute or cfg.DATASET.ATTRIBUTE_TYPE
     if args.seed is not None:
         np.random.seed(args.seed)
     n_client, by_attr = _counts(trainer, attribute, users)
+    dp = dp_config(args, trainer)
     trainer.fed_before_train()
     # Only the trainable tensors travel: the reference averages the whole state_dict, but frozen tensors are
     # identical on every client, so their weighted mean is the tensor itself up to one rounding per round
@@ -156,10 +199,21 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
     local_ctx: Dict[int, Tensor] = {}
     local_s: Dict[int, Dict[str, Tensor]] = {}
     hist = {"acc": [], "err": [], "f1": [], "auc": [], "epoch": [], "time": []}
+    agg = None
+    if dp is not None:
+        # with dp the round boundary is the flat-buffer aggregator of run_fedotplora_ranks (no process group: its sum is
+        # this process's), so both drivers clip the same vector and draw the same flat-index noise
+        from .fedavg import FedAvgAggregator
+        params, lo = trainer.engine.params, trainer.engine.cfg.lora
+        trainer.model.load_state_dict(global_weights, strict=False)
+        agg = FedAvgAggregator(params.flat, params.offsets, lo.num_groups, lo.rank, shared_half_s=args.shared_half_s,
+                               beta=0.999, dp=dp)
     start = time.time()
     for epoch in range(args.round):
         idxs_users = select_clients(epoch, args, users)
         log(f"------------local train start epoch: {epoch} -------------")
+        if agg is not None:
+            agg.begin(round=epoch)
         for idx in idxs_users:
             trainer.model.load_state_dict(global_weights if epoch == 0 else local_weights_per[idx], strict=False)
             trainer.train(idx=idx, global_epoch=epoch, is_fed=True, is_last_client=idx == idxs_users[-1])
@@ -167,8 +221,15 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
             local_ctx[idx] = copy.deepcopy(lw["prompt_learner.ctx"][args.avg_prompt:args.num_prompt])
             local_s[idx] = copy.deepcopy({k: v for k, v in lw.items() if "lora_S" in k})
             local_weights[idx] = lw
-        global_weights = average_weights_ema(global_weights, local_weights, idxs_users, n_client, by_attr, epoch,
-                                             args.round, shared_half_s=args.shared_half_s)
+            if agg is not None:
+                agg.add(params.flat, idx, idxs_users, n_client, by_attr)
+        if agg is None:
+            global_weights = average_weights_ema(global_weights, local_weights, idxs_users, n_client, by_attr, epoch,
+                                                 args.round, shared_half_s=args.shared_half_s)
+        else:
+            g = agg.finish(epoch, args.round, grouped=by_attr is not None)
+            global_weights = {k: g[off:off + int(np.prod(shp))].view(shp).clone() for k, (off, shp) in params.offsets.items()}
+            _dp_log(hist, dp, agg.dp_stats, epoch, log)
         all_users = list(args.idxs_users_test) if len(args.idxs_users_test) > 0 else list(range(users))
         results = []
         for idx in all_users:
@@ -209,8 +270,9 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
     params = trainer.engine.params
     flat, offsets = params.flat, params.offsets
     lo = trainer.engine.cfg.lora
+    dp = dp_config(args, trainer)
     trainer.fed_before_train()
-    agg = FedAvgAggregator(flat, offsets, lo.num_groups, lo.rank, shared_half_s=args.shared_half_s, beta=0.999)
+    agg = FedAvgAggregator(flat, offsets, lo.num_groups, lo.rank, shared_half_s=args.shared_half_s, beta=0.999, dp=dp)
     global_flat = agg.global_prev                                    # updated in place by agg.finish()
     per_client = {i: global_flat.clone() for i in range(users)}      # personalised flat buffers (this rank's view)
     ctx_off, ctx_shape = offsets["prompt_learner.ctx"]
@@ -238,7 +300,7 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
         pick = [select_clients(epoch, args, users) if rank == 0 else None]
         dist.broadcast_object_list(pick, src=0)
         idxs_users = [int(u) for u in pick[0]]
-        agg.begin()
+        agg.begin(round=epoch)
         if has_buf:
             agg_buf.begin()
         local_after: Dict[int, Tensor] = {}
@@ -272,6 +334,10 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
         agg.finish(epoch, args.round, grouped=by_attr is not None)
         if has_buf:
             agg_buf.finish(epoch, args.round, grouped=False)
+        if dp is not None:                                           # every rank learns every client's norm (one sync per round)
+            parts = [None] * world
+            dist.all_gather_object(parts, agg.dp_stats)
+            _dp_log(hist, dp, {c: v for part in parts for c, v in part.items()}, epoch, log if rank == 0 else (lambda *_: None))
         # personalisation needs every trained client's local prompts / lora_S on every rank that may test it:
         # exchange them (a few KB) with one more all-reduce of a zero-padded buffer
         keep = torch.zeros(users, flat.numel(), device=flat.device) if args.idxs_users_train else None

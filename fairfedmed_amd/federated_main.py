@@ -105,6 +105,12 @@ def build_parser() -> argparse.ArgumentParser:
       help="INPUT.INTERPOLATE_POS: run a ViT at an INPUT.SIZE other than its checkpoint's (a multiple of the patch size) with "
            "the positional embedding resized (bicubic) at load - an extension: the reference asserts the two sizes equal")
     a("--compat-sequential-optimizer", action="store_true")
+    a("--dp_clip", type=float, default=0.0,
+      help="client-level differential privacy at the round boundary: L2 bound on one client's update over the flat trainable "
+           "buffer (0 = off; an extension beyond the reference)")
+    a("--dp_noise", type=float, default=0.0, help="noise multiplier z of the per-round Gaussian mechanism (0: clip only)")
+    a("--dp_seed", type=int, default=None, help="key of the noise generator (default: --seed when positive, else 0)")
+    a("--dp_delta", type=float, default=1e-5, help="the delta the logged epsilon is stated for")
     a("--save-trainable-only", action="store_true",
       help="global_client{idx}_final.pth without the frozen CLIP tensors (the reference saves the full state_dict)")
     return p
@@ -188,6 +194,17 @@ def check_scope(args, cfg) -> None:
         raise NotImplementedError("--unfreeze_image_encoder must be set: without it no FairLoRA adapter is injected")
 
 
+def fed_args(args):
+    """The parsed command line as the round loop's FedArgs."""
+    from . import federated as F
+    return F.FedArgs(num_users=args.num_users, frac=args.frac, round=args.round, avg_prompt=args.avg_prompt,
+                     num_prompt=args.num_prompt, idxs_users_train=args.idxs_users_train,
+                     idxs_users_test=args.idxs_users_test, shared_half_s=args.shared_half_s, local_s=args.lora_local_s,
+                     seed=args.seed if args.seed > 0 else None,
+                     compat_sequential_optimizer=args.compat_sequential_optimizer,
+                     dp_clip=args.dp_clip, dp_noise=args.dp_noise, dp_seed=args.dp_seed, dp_delta=args.dp_delta)
+
+
 def main(argv: Optional[List[str]] = None, log=print, cfg_hook=None):
     """cfg_hook(cfg): last-minute edits of the config tree (tests use it to select a reduced model geometry)."""
     import torch.distributed as dist
@@ -252,11 +269,7 @@ def main(argv: Optional[List[str]] = None, log=print, cfg_hook=None):
         for idx, r in results.items():
             log(f"client {idx}: acc {r[0]:.3f} err {r[1]:.3f} macro_f1 {r[2]:.3f} auc {r[3]:.4f}")
         return {"eval": results}
-    fargs = F.FedArgs(num_users=args.num_users, frac=args.frac, round=args.round, avg_prompt=args.avg_prompt,
-                      num_prompt=args.num_prompt, idxs_users_train=args.idxs_users_train,
-                      idxs_users_test=args.idxs_users_test, shared_half_s=args.shared_half_s, local_s=args.lora_local_s,
-                      seed=args.seed if args.seed > 0 else None,
-                      compat_sequential_optimizer=args.compat_sequential_optimizer)
+    fargs = fed_args(args)
     rank = dist.get_rank() if ranks else 0
     hist = (F.run_fedotplora_ranks if ranks else F.run_fedotplora)(tr, fargs, log=log if rank == 0 else (lambda *_: None))
     if rank == 0:

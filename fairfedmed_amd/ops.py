@@ -955,6 +955,60 @@ def fedavg_finish(avg: Tensor, prev: Tensor, out: Tensor, s_offsets: Optional[Te
                                        L.ptr(s_offsets), n_s, G, r, int(shared_half_s), beta, L.stream_ptr())
 
 
+def _seed64(seed: int) -> int:
+    """A 64-bit seed as the int64_t the ABI carries (two's complement of the unsigned value)."""
+    seed &= (1 << 64) - 1
+    return seed - (1 << 64) if seed >> 63 else seed
+
+
+def dp_norm_ws_bytes(n: int) -> int:
+    """Bytes of the fp64 scratch of dp_norm / dp_privatise for n elements (ffm_dp_norm_ws_bytes; needs no GPU)."""
+    b = L.load().ffm_dp_norm_ws_bytes(int(n))
+    if b <= 0:
+        L.check(int(b) or -1, "ffm_dp_norm_ws_bytes")
+    return int(b)
+
+
+def dp_scratch(n: int, device) -> Tensor:
+    return torch.empty(dp_norm_ws_bytes(n) // 8, dtype=torch.float64, device=device)
+
+
+def dp_norm(theta: Tensor, g: Tensor, scratch: Tensor) -> None:
+    """scratch <- fixed-order fp64 partial sums of (theta - g)^2 (ffm_dp_norm); dp_privatise with the same n reads them."""
+    _dev(theta, g, scratch)
+    assert theta.numel() == g.numel() and scratch.dtype == torch.float64 and scratch.is_contiguous()
+    assert scratch.numel() * 8 >= dp_norm_ws_bytes(theta.numel())
+    _call("ffm_dp_norm", L.ptr(_f32(theta)), L.ptr(_f32(g)), theta.numel(), L.ptr(scratch), L.stream_ptr())
+
+
+def dp_privatise(theta: Tensor, g: Tensor, w: Tensor, out: Tensor, scratch: Tensor, clip: float, sigma: float, seed: int,
+                 round: int, client: int, accumulate: bool = False, stats: Optional[Tensor] = None) -> None:
+    """out (+)= the clipped, weighted and noised contribution of one client (ffm_dp_privatise).
+    `scratch` holds what dp_norm left for the same theta and g; stats (fp32 [2], optional) receives {norm, clip factor}."""
+    _dev(theta, g, w, out, scratch, stats)
+    n = theta.numel()
+    assert g.numel() == n and w.numel() == n and out.numel() == n
+    assert scratch.dtype == torch.float64 and scratch.is_contiguous() and scratch.numel() * 8 >= dp_norm_ws_bytes(n)
+    assert stats is None or stats.numel() >= 2
+    _call("ffm_dp_privatise", L.ptr(_f32(theta)), L.ptr(_f32(g)), L.ptr(_f32(w)), L.ptr(_f32(out)), n, L.ptr(scratch),
+          float(clip), float(sigma), _seed64(seed), int(round), int(client), int(accumulate), L.ptr(_f32(stats)),
+          L.stream_ptr())
+
+
+def dp_noise(out: Tensor, sigma: float, seed: int, round: int, client: int) -> None:
+    """out[i] = sigma * xi[i], the noise share of (seed, round, client) alone (ffm_dp_noise)."""
+    _dev(out)
+    _call("ffm_dp_noise", L.ptr(_f32(out)), out.numel(), float(sigma), _seed64(seed), int(round), int(client),
+          L.stream_ptr())
+
+
+def dp_philox(out: Tensor, seed: int, c0: int = 0, c1: int = 0, c2: int = 0, c3: int = 0) -> None:
+    """out[j] (int32) = word j & 3 of Philox4x32-10(counter (c0 + (j >> 2), c1, c2, c3), key = the halves of seed)."""
+    _dev(out)
+    assert out.dtype == torch.int32 and out.is_contiguous()
+    _call("ffm_dp_philox", L.ptr(out), out.numel(), _seed64(seed), int(c0), int(c1), int(c2), int(c3), L.stream_ptr())
+
+
 def cast_from_f32(src: Tensor, dtype: torch.dtype) -> Tensor:
     _dev(src)
     dst = torch.empty(src.shape, dtype=dtype, device=src.device)

@@ -55,7 +55,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* The value in use for the diagnostic switch whose environment variable is `name` ("FFM_PANEL", "FFM_ATTN", ...: the rows
@@ -765,6 +765,34 @@ int ffm_scale_acc(const float* p, const float* w, float* acc, int64_t n, void* s
  * then EMA with the previous global: p = (1-beta)*avg + beta*prev. */
 int ffm_fedavg_finish(float* avg, const float* prev, float* out, int64_t n, const int64_t* s_offsets,
                       int n_s, int G, int r, int shared_half_s, float beta, void* stream);
+
+/*
+ * Client-level differential privacy at the round boundary (an extension: the reference hands raw
+ * weights to average_weights_EMA).  For one client with flat buffer theta, previous global g and per-element weights w:
+ *     nu = || theta - g ||_2   (difference in fp32, squares and sums in fp64, fixed order)
+ *     s  = 1 if nu <= clip;  clip / nu if clip < nu < inf;  0 if nu is not finite (a NaN / Inf anywhere in theta)
+ *     c  = w * theta (s == 1: the product of ffm_scale_by)  |  w * (g + s * (theta - g))  |  w * g (s == 0: theta is not read)
+ *          + sigma * xi   (sigma > 0 only)
+ * xi[i] is lane i & 3 of the Box-Muller pairs (r0 cos 2 pi u1, r0 sin 2 pi u1, r2 cos 2 pi u3, r2 sin 2 pi u3), r_j =
+ * sqrt(-2 ln u_j), u_j = ((x_j >> 9) + 0.5) 2^-23, x = Philox4x32-10(counter (i >> 2, round, client, 0), key (low, high word
+ * of seed)), i counted from the pointer passed in: independent of alignment, launch geometry, rank and world size.
+ *
+ * ffm_dp_norm_ws_bytes: bytes of the fp64 scratch for n elements (needs no GPU; FFM_EINVAL for n <= 0 or n > 2^34).
+ * ffm_dp_norm: scratch <- per-block partial sums of (theta - g)^2.  No atomics, no read-back.
+ * ffm_dp_privatise: every block re-sums the partials of the ffm_dp_norm call with the SAME n in the same order, forms s and
+ * writes out = c (accumulate == 0) or out = out + c (product and sum rounded separately, as ffm_scale_acc).  stats (may be
+ * NULL) receives {nu, s} as fp32.  16-byte loads and stores when theta, g, w and out are all 16-byte aligned, element by
+ * element otherwise - the same values.  FFM_EINVAL: a NULL pointer (stats excepted), n <= 0, clip <= 0, sigma < 0 or not finite.
+ */
+int64_t ffm_dp_norm_ws_bytes(int64_t n);
+int ffm_dp_norm(const float* theta, const float* g, int64_t n, void* scratch, void* stream);
+int ffm_dp_privatise(const float* theta, const float* g, const float* w, float* out, int64_t n, const void* scratch,
+                     float clip, float sigma, int64_t seed, int round, int client, int accumulate, float* stats,
+                     void* stream);
+/* Test-facing: out[i] = sigma * xi[i] alone, and the raw generator: out[j] = word j & 3 of Philox4x32-10(counter
+ * (c0 + (j >> 2), c1, c2, c3), key (low, high word of seed)); the counter words are taken modulo 2^32. */
+int ffm_dp_noise(float* out, int64_t n, float sigma, int64_t seed, int round, int client, void* stream);
+int ffm_dp_philox(int32_t* out, int64_t n, int64_t seed, int64_t c0, int64_t c1, int64_t c2, int64_t c3, void* stream);
 
 /* dtype conversion helpers (weight preparation at load time). */
 int ffm_cast_f32_to(const float* src, void* dst, int64_t n, int dtype, void* stream);
