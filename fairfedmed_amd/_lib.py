@@ -106,6 +106,8 @@ SIGNATURES = {
     "ffm_eval_counts": [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "ffm_eval_counts_ws_bytes": [_i32],
     "ffm_eval_counts_sorted": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp],
+    "ffm_eval_boot_ws_bytes": [_i32, _i32],
+    "ffm_eval_boot_counts": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _i64, _vp],
     "ffm_ot_head_fwd": [_vp] * 10 + [_i32] * 6 + [_f32, _f32, _i32, _f32, _i32, _vp],
     "ffm_ot_head_bwd": [_vp] * 8 + [_i32] * 6 + [_vp],
     "ffm_expand_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],

@@ -2,6 +2,7 @@
 // theta - g over the flat trainable buffer, and the clipped, weighted and noised contribution c_k of that client to the
 // round's sum.  Two launches per client; the clip factor is formed on the device and never read back.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -19,20 +20,6 @@ inline int elem_blocks(int64_t n) {
     return (int)(b > kMaxBlocks ? kMaxBlocks : b);
 }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// Philox4x32-10 (Salmon et al., SC'11; Random123's constants)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t x[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
 
 // The four standard normals of group q (elements 4q .. 4q+3 counted from the pointer passed in): counter (q, t, k, 0), key the
 // two halves of the seed (low word first); u_j = ((x_j >> 9) + 0.5) 2^-23 is exact in fp32 and strictly inside (0, 1);

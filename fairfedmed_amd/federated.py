@@ -87,6 +87,32 @@ def _dp_log(hist, dp, stats: Dict[int, tuple], epoch: int, log) -> None:
         + f"  clipped at {dp.clip:g}: {clipped}  epsilon <= {hist['dp_epsilon'][-1]:.4g} (delta {dp.delta:g})")
 
 
+def _bootstrap_on(trainer) -> bool:
+    return int(getattr(getattr(trainer.cfg, "TEST", None), "BOOTSTRAP", 0) or 0) > 0
+
+
+def _ci_log(hist, ci_by_client: Dict[int, dict], results: Dict[int, dict], epoch: int, log) -> None:
+    """One round's {client: last_results["ci"]} into the history, and one line per client: AUC, ES-AUC and the AUC gap (max -
+    min group AUC) of every attribute column, each with its interval.  Intervals are per client: none is formed across them."""
+    hist.setdefault("ci", []).append({c: ci_by_client[c] for c in sorted(ci_by_client)})
+
+    def fmt(x, iv):
+        head = "n/a" if x is None else f"{x:.4f}"
+        return head + (" [no interval]" if iv is None else f" [{iv[0]:.4f}, {iv[1]:.4f}]")
+
+    for c in sorted(ci_by_client):
+        ci, res = ci_by_client[c], results.get(c, {})
+        es, ga = res.get("esaucs_by_attrs", []), res.get("aucs_by_attrs", [])
+        auc = res.get("overall_auc")
+        cols = [f"auc % {fmt(None if auc is None else 100.0 * auc, ci['auc'])}"]      # in percent, as test() returns it
+        for a in range(len(ci["esaucs_by_attrs"])):
+            gap = float(np.max(ga[a]) - np.min(ga[a])) if a < len(ga) and len(ga[a]) else None
+            cols.append(f"attr {a}: es-auc {fmt(es[a] if a < len(es) else None, ci['esaucs_by_attrs'][a])}"
+                        f" auc gap {fmt(gap, ci['auc_gap_by_attrs'][a])}")
+        log(f"round {epoch} client {c}: " + "  ".join(cols) + f"  ({100 * ci['level']:g} % bootstrap, {ci['replicates']} "
+            f"replicates, degenerate {ci['degenerate']})")
+
+
 def average_weights_ema(w_g: Dict[str, Tensor], w: Dict[int, Dict[str, Tensor]], idxs_users: Sequence[int],
                         datanumber_client: Sequence[int], datanumber_client_by_attr, epoch: int, max_epoch: int,
                         beta: float = 0.999, shared_half_s: bool = False) -> Dict[str, Tensor]:
@@ -184,6 +210,7 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
         np.random.seed(args.seed)
     n_client, by_attr = _counts(trainer, attribute, users)
     dp = dp_config(args, trainer)
+    boot = _bootstrap_on(trainer)
     trainer.fed_before_train()
     # Only the trainable tensors travel: the reference averages the whole state_dict, but frozen tensors are
     # identical on every client, so their weighted mean is the tensor itself up to one rounding per round
@@ -231,11 +258,15 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
             global_weights = {k: g[off:off + int(np.prod(shp))].view(shp).clone() for k, (off, shp) in params.offsets.items()}
             _dp_log(hist, dp, agg.dp_stats, epoch, log)
         all_users = list(args.idxs_users_test) if len(args.idxs_users_test) > 0 else list(range(users))
-        results = []
+        results, ci, full = [], {}, {}
         for idx in all_users:
             local_weights_per[idx] = personalize(global_weights, idx, args, local_ctx, local_s)
             trainer.model.load_state_dict(local_weights_per[idx], strict=False)
             results.append(trainer.test(idx=idx, current_epoch=epoch))
+            if boot:
+                ci[idx], full[idx] = trainer.last_results["ci"], dict(trainer.last_results)
+        if boot:
+            _ci_log(hist, ci, full, epoch, log)
         for name, col in (("acc", 0), ("err", 1), ("f1", 2)):
             hist[name].append(sum(r[col] for r in results) / len(results))
         if len(results[0]) > 3:
@@ -271,6 +302,7 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
     flat, offsets = params.flat, params.offsets
     lo = trainer.engine.cfg.lora
     dp = dp_config(args, trainer)
+    boot = _bootstrap_on(trainer)
     trainer.fed_before_train()
     agg = FedAvgAggregator(flat, offsets, lo.num_groups, lo.rank, shared_half_s=args.shared_half_s, beta=0.999, dp=dp)
     global_flat = agg.global_prev                                    # updated in place by agg.finish()
@@ -346,7 +378,7 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
                 keep[idx] = f
             dist.all_reduce(keep, op=dist.ReduceOp.SUM)
         all_users = list(args.idxs_users_test) if len(args.idxs_users_test) > 0 else list(range(users))
-        results = []
+        results, ci, full = [], {}, {}
         for idx in all_users:
             per_client[idx] = global_flat.clone()
             if has_buf:
@@ -363,9 +395,16 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
             if has_buf:
                 eng.load_buffers_flat(per_client_buf[idx])
             results.append((idx, trainer.test(idx=idx, current_epoch=epoch)))
+            if boot:
+                ci[idx], full[idx] = trainer.last_results["ci"], dict(trainer.last_results)
         gathered = [None] * world
         dist.all_gather_object(gathered, results)
         flat_res = [r for part in gathered for r in part]
+        if boot:                                                     # every rank learns every client's intervals
+            parts = [None] * world
+            dist.all_gather_object(parts, (ci, full))
+            _ci_log(hist, {c: v for part in parts for c, v in part[0].items()},
+                    {c: v for part in parts for c, v in part[1].items()}, epoch, log if rank == 0 else (lambda *_: None))
         for name, col in (("acc", 0), ("err", 1), ("f1", 2), ("auc", 3)):
             vals = [r[1][col] for r in flat_res if len(r[1]) > col]
             if vals:

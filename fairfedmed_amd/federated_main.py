@@ -111,6 +111,11 @@ def build_parser() -> argparse.ArgumentParser:
     a("--dp_noise", type=float, default=0.0, help="noise multiplier z of the per-round Gaussian mechanism (0: clip only)")
     a("--dp_seed", type=int, default=None, help="key of the noise generator (default: --seed when positive, else 0)")
     a("--dp_delta", type=float, default=1e-5, help="the delta the logged epsilon is stated for")
+    a("--bootstrap", type=int, default=0,
+      help="TEST.BOOTSTRAP: replicates of the percentile bootstrap behind the intervals test() adds to its results (0 = off; "
+           "binary tasks, device metrics; an extension beyond the reference)")
+    a("--bootstrap_seed", type=int, default=0, help="TEST.BOOTSTRAP_SEED: key of the resampling generator")
+    a("--ci_level", type=float, default=0.95, help="TEST.CI_LEVEL: coverage of the reported intervals")
     a("--save-trainable-only", action="store_true",
       help="global_client{idx}_final.pth without the frozen CLIP tensors (the reference saves the full state_dict)")
     return p
@@ -154,7 +159,8 @@ def setup_cfg(args) -> NS:
                  ADAM_BETA1=0.9, ADAM_BETA2=0.999, RMSPROP_ALPHA=0.99, WARMUP_EPOCH=-1, WARMUP_TYPE="linear",
                  WARMUP_CONS_LR=1e-5, WARMUP_MIN_LR=1e-5, WARMUP_RECOUNT=True),
         TRAIN=NS(CHECKPOINT_FREQ=0, PRINT_FREQ=10, METRICS_EVERY=1),
-        TEST=NS(BATCH_SIZE=args.test_batch_size, NO_TEST=False, EVALUATOR="Classification_oph"),
+        TEST=NS(BATCH_SIZE=args.test_batch_size, NO_TEST=False, EVALUATOR="Classification_oph", BOOTSTRAP=args.bootstrap,
+                BOOTSTRAP_SEED=args.bootstrap_seed, CI_LEVEL=args.ci_level),
         TRAINER=NS(NAME=args.trainer, LAMBDA_FAIRNESS=args.lambda_fairness, FAIRNESS_GRAD=args.fairness_grad,
                    GLP_OT=NS(N_CTX=args.n_ctx, CSC=False, CTX_INIT=args.ctx_init, PREC=args.prec,
                              CLASS_TOKEN_POSITION="end", N=args.num_prompt, THRESH=args.thresh, EPS=args.eps, OT=args.OT,

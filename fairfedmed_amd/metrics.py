@@ -197,3 +197,73 @@ def comprehensive_scores_from_counts(counts_by_attr) -> dict:
         out["dpds"].append(float(max(sel) - min(sel)))
         out["eods"].append(float(max(max(tpr) - min(tpr), max(fpr) - min(fpr))))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Percentile-bootstrap intervals from the replicate tables of ffm_eval_boot_counts: every
+# replicate is scored by the functions above, so an interval is an interval of exactly the number that is reported.
+# ------------------------------------------------------------------------------------------------------------
+def _single_class(r) -> bool:
+    return int(r[N_POS]) == 0 or int(r[N_NEG]) == 0
+
+
+def _interval(values, level: float):
+    """(lo, hi, se): the percentile interval (linear interpolation) and the standard deviation (ddof = 1)."""
+    v = np.asarray(values, dtype=np.float64)
+    lo, hi = np.percentile(v, [100.0 * (1.0 - level) / 2.0, 100.0 * (1.0 + level) / 2.0])
+    return float(lo), float(hi), float(np.std(v, ddof=1)) if len(v) > 1 else float("nan")
+
+
+def bootstrap_intervals(tables, boot_tables, level: float = 0.95, max_degenerate: float = 0.05) -> dict:
+    """Intervals of the scores of basic_from_counts / comprehensive_scores_from_counts.  tables: the full-sample count
+    tables [n_attr, G + 2, 10]; boot_tables: their bootstrap replicates [n_attr, B, G + 2, 10].
+
+    A replicate is degenerate for an attribute if its 'all' row lacks a class, or if a group that is present in the full
+    sample has no sample or a single class in it: such a set would score AUC = 1 by the single-class convention.  Degenerate
+    replicates are left out of that attribute's intervals and counted ("degenerate"); when their share exceeds
+    max_degenerate every interval of that attribute is None and a warning is logged.  The three scores of the 'all' row
+    leave out the replicates whose 'all' row lacks a class, under the same cap.
+
+    Returns {"level", "replicates", "degenerate": [per attribute], "accuracy", "macro_f1", "auc": (lo, hi, se) in percent as
+    basic_from_counts reports them, and per attribute "aucs_by_attrs" (one triple per group present in the full sample),
+    "esaucs_by_attrs", "auc_gap_by_attrs" (max - min group AUC), "dpds", "eods"}."""
+    import logging
+    log = logging.getLogger(__name__)
+    tables, boot = np.asarray(tables), np.asarray(boot_tables)
+    if boot.ndim != 4 or tables.ndim != 3 or boot.shape[0] != tables.shape[0] or boot.shape[2:] != tables.shape[1:]:
+        raise ValueError(f"bootstrap_intervals: tables {tables.shape} and replicate tables {boot.shape} do not match")
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"bootstrap_intervals: level must lie in (0, 1), got {level}")
+    n_attr, B = boot.shape[:2]
+    out = {"level": float(level), "replicates": int(B), "degenerate": [], "aucs_by_attrs": [], "esaucs_by_attrs": [],
+           "auc_gap_by_attrs": [], "dpds": [], "eods": []}
+
+    keep = [r for r in range(B) if not _single_class(boot[0][r][-1])]
+    if B - len(keep) > max_degenerate * B or not keep:
+        log.warning("bootstrap: %d of %d replicates lack a class; no interval for accuracy, macro-F1 and AUC", B - len(keep), B)
+        out.update(accuracy=None, macro_f1=None, auc=None)
+    else:
+        basic = np.array([basic_from_counts(boot[0][r]) for r in keep])
+        out.update(accuracy=_interval(basic[:, 0], level), macro_f1=_interval(basic[:, 2], level),
+                   auc=_interval(basic[:, 3], level))
+
+    for a in range(n_attr):
+        present = [g for g in range(tables.shape[1] - 2) if int(tables[a][g][N_POS]) + int(tables[a][g][N_NEG]) > 0]
+        keep = [r for r in range(B)
+                if not _single_class(boot[a][r][-1]) and not any(_single_class(boot[a][r][g]) for g in present)]
+        out["degenerate"].append(B - len(keep))
+        if B - len(keep) > max_degenerate * B or not keep or not present:
+            if present:
+                log.warning("bootstrap: attribute %d: %d of %d replicates are degenerate (a group without samples or with one "
+                            "class), more than %g of them; no interval is formed", a, B - len(keep), B, max_degenerate)
+            for k in ("aucs_by_attrs", "esaucs_by_attrs", "auc_gap_by_attrs", "dpds", "eods"):
+                out[k].append(None)
+            continue
+        scores = [comprehensive_scores_from_counts([boot[a][r]]) for r in keep]
+        ga = np.array([s["aucs_by_attrs"][0] for s in scores])                         # [kept, present groups]
+        out["aucs_by_attrs"].append([_interval(ga[:, j], level) for j in range(ga.shape[1])])
+        out["esaucs_by_attrs"].append(_interval([s["esaucs_by_attrs"][0] for s in scores], level))
+        out["auc_gap_by_attrs"].append(_interval(ga.max(1) - ga.min(1), level))
+        out["dpds"].append(_interval([s["dpds"][0] for s in scores], level))
+        out["eods"].append(_interval([s["eods"][0] for s in scores], level))
+    return out

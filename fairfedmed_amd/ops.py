@@ -611,6 +611,63 @@ def eval_counts(prob: Tensor, label: Tensor, attr: Optional[Tensor], num_groups:
     return out
 
 
+EVAL_BOOT_WS_BUDGET = 256 << 20     # bytes of workspace the default chunk of eval_boot_counts stays under
+EVAL_BOOT_MAX_CHUNK = 65535         # csrc/evalboot.hip: the replicates of a chunk ride in gridDim.y
+
+
+def eval_boot_chunk(N: int, B: int) -> int:
+    """The default chunk of eval_boot_counts: the most replicates (at most B) whose workspace stays under
+    EVAL_BOOT_WS_BUDGET; 1 where even a single replicate's does not."""
+    size = L.load().ffm_eval_boot_ws_bytes
+    if int(size(N, 1)) <= 0:
+        raise RuntimeError("ffm_eval_boot_ws_bytes failed")
+    lo, hi = 1, int(max(1, min(B, EVAL_BOOT_MAX_CHUNK)))           # the size grows with the chunk: bisect
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if int(size(N, mid)) <= EVAL_BOOT_WS_BUDGET:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def eval_boot_counts(prob: Tensor, label: Tensor, attr: Optional[Tensor], num_groups: int, B: int, seed: int, tag: int = 0,
+                     chunk: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """B bootstrap replicates of eval_counts' table (ffm_eval_boot_counts): int64 [B, G + 2, 10] on the device; replicate r
+    is the table of the test set resampled with replacement by the draws of (seed, tag, r) (include/ffm_hip.h), which do
+    not depend on attr, num_groups or chunk.  chunk: replicates processed at a time; it sizes the workspace and changes no
+    result.  chunk=None takes the most replicates that keep the workspace under EVAL_BOOT_WS_BUDGET = 256 MiB (89 N
+    bytes for the sorted orders, the sort's temporary storage, and 20 N bytes per replicate of the chunk).  The workspace is allocated and held
+    here, so the call refuses to be recorded into a launch plan."""
+    _dev(prob, label, attr)
+    N = prob.shape[0]
+    assert prob.dtype == torch.float32 and prob.dim() == 2 and prob.shape[1] == 2 and prob.is_contiguous()
+    assert label.dtype == torch.int64 and label.is_contiguous() and label.numel() == N
+    assert attr is None or (attr.dtype == torch.int64 and attr.is_contiguous() and attr.numel() == N)
+    B = int(B)
+    if B <= 0:
+        raise ValueError(f"eval_boot_counts needs B >= 1 replicates, got {B}")
+    if recording():
+        # refused BEFORE anything is allocated or launched, as eval_counts(method='sort') is
+        raise RuntimeError("eval_boot_counts holds a temporary workspace and cannot be recorded")
+    if chunk is None:
+        chunk = eval_boot_chunk(N, B)
+    chunk = int(chunk)
+    if not 1 <= chunk <= EVAL_BOOT_MAX_CHUNK:
+        raise ValueError(f"eval_boot_counts: chunk must lie in 1..{EVAL_BOOT_MAX_CHUNK}, got {chunk}")
+    if out is None:
+        out = torch.empty(B, num_groups + 2, EVAL_SLOTS, device=prob.device, dtype=torch.int64)
+    assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (B, num_groups + 2, EVAL_SLOTS) and out.is_cuda
+    nbytes = int(L.load().ffm_eval_boot_ws_bytes(N, chunk))
+    if nbytes <= 0:
+        raise RuntimeError("ffm_eval_boot_ws_bytes failed")
+    ws = torch.empty(nbytes + 256, device=prob.device, dtype=torch.uint8)          # device memory is PyTorch's job
+    off = (-ws.data_ptr()) % 256
+    _call("ffm_eval_boot_counts", L.ptr(prob), L.ptr(label), L.ptr(attr), N, num_groups, B, chunk, int(seed), int(tag),
+          L.ptr(out), ws.data_ptr() + off, nbytes, L.stream_ptr())
+    return out
+
+
 def attention_fwd(qkv: Tensor, out: Tensor, lse: Optional[Tensor], B: int, Ltok: int, heads: int,
                   causal: bool = False) -> Tensor:
     _dev(qkv, out, lse)

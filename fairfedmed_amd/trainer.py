@@ -25,8 +25,8 @@ import torch
 from . import config as C
 from . import synth
 from . import ops
-from .metrics import (auc_macro_ovr, basic_from_counts, comprehensive_scores, comprehensive_scores_from_counts,
-                      macro_f1)
+from .metrics import (auc_macro_ovr, basic_from_counts, bootstrap_intervals, comprehensive_scores,
+                      comprehensive_scores_from_counts, macro_f1)
 from .model import CustomCLIP
 from .optim import build_lr_schedule, build_optim_spec
 from .registry import TRAINER_REGISTRY
@@ -486,7 +486,15 @@ class GLP_OT_SVLoRA:
     def test(self, split=None, is_global=False, current_epoch=0, idx=-1, global_test=False):
         """[acc, err, macro_f1, auc] over the client's test loader, all four in percent as the reference's evaluator
         stores them (SimpleTrainer.test, Dassl/dassl/engine/trainer.py:523-569; evaluation/evaluator_oph.py:66-96:
-        auc = 100 * compute_auc; federated_main.py:685-690 indexes [0..3])."""
+        auc = 100 * compute_auc; federated_main.py:685-690 indexes [0..3]).
+
+        TEST.BOOTSTRAP = B > 0 (an extension beyond the reference) also leaves last_results["ci"]: percentile-bootstrap
+        intervals at TEST.CI_LEVEL from B resamples of the test set (metrics.bootstrap_intervals)."""
+        n_boot = int(getattr(self.cfg.TEST, "BOOTSTRAP", 0) or 0)
+        if n_boot > 0 and (self.num_classes != 2 or getattr(self.cfg.TEST, "HOST_METRICS", False)):
+            # refused before anything runs: the setting is never ignored
+            raise NotImplementedError("TEST.BOOTSTRAP > 0 needs a binary task and the device metrics (TEST.HOST_METRICS off): "
+                                      "the intervals are formed from the replicate tables of ffm_eval_boot_counts")
         self.set_model_mode("eval")
         probs, labels, attrs_all = [], [], []
         # one evaluation session: the parameters do not move inside a test(), so the rank operands are packed and the text
@@ -510,6 +518,14 @@ class GLP_OT_SVLoRA:
             self.last_results = {"accuracy": res[0], "error_rate": res[1]}
             if tables[0][-1][0] > 0 and tables[0][-1][1] > 0:
                 self.last_results.update(comprehensive_scores_from_counts(tables))
+            if n_boot > 0:
+                # percentile-bootstrap intervals: the same tables for n_boot resamples of the test
+                # set, one call per attribute column and one D2H copy.  The client index is the tag and the round is not part
+                # of it: every round sees the same resamples (common random numbers), every column the same ones too
+                seed = int(getattr(self.cfg.TEST, "BOOTSTRAP_SEED", 0) or 0)
+                boot = torch.stack([ops.eval_boot_counts(prob_d, y_d, attrs_d[a].contiguous(), G, n_boot, seed, tag=idx + 1)
+                                    for a in range(attrs_d.shape[0])]).cpu().numpy()
+                self.last_results["ci"] = bootstrap_intervals(tables, boot, level=float(getattr(self.cfg.TEST, "CI_LEVEL", 0.95)))
             return res
         prob = prob_d.cpu().numpy()
         y = y_d.cpu().numpy()

@@ -55,7 +55,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* The value in use for the diagnostic switch whose environment variable is `name` ("FFM_PANEL", "FFM_ATTN", ...: the rows
@@ -631,6 +631,29 @@ int ffm_eval_counts(const float* prob, const int64_t* label, const int64_t* attr
 int64_t ffm_eval_counts_ws_bytes(int N);
 int ffm_eval_counts_sorted(const float* prob, const int64_t* label, const int64_t* attr, int N, int G, uint64_t* out,
                            void* workspace, int64_t workspace_bytes, void* stream);
+/*
+ * B bootstrap replicates of that table (csrc/evalboot.hip): out[r], r = 0..B-1, is the table ffm_eval_counts would produce
+ * for the test set resampled with replacement, (prob[idx_k], label[idx_k], attr[idx_k]) for k = 0..N-1, integer for
+ * integer.  prob, label, attr (may be NULL), G, rows and slots as above; out: uint64 [B][G + 2][FFM_EVAL_SLOTS], zeroed by
+ * the call.  The resample of replicate r:
+ *   x     = Philox4x32-10(counter (k >> 1, r, tag, 0x544F4F42), key = (low word of seed, high word of seed)), the
+ *           generator and key rule of ffm_dp_philox
+ *   x64   = x[2 (k & 1)] | x[2 (k & 1) + 1] << 32
+ *   idx_k = (x64 * N) >> 64, the high word of the 128-bit product
+ *   m_r[i] = #{k : idx_k = i}, the multiplicity of sample i
+ * The draws depend on (seed, tag, r, k) and on nothing else - not on attr, G or chunk - so calls that differ only in the
+ * attribute column see the same resamples (equal 'all' rows, paired group differences).  In terms of m_r: the sample and
+ * confusion counts of a row are the sums of m_r[i] over its samples; win_c (tie_c) is the sum of m_r[i] m_r[j] over the
+ * pairs of a positive i and a negative j of column c in that row with s_c[i] > s_c[j] (s_c[i] == s_c[j]).
+ * One sort per column and scope for the whole call; then the replicates in chunks of `chunk` (1..65535, FFM_EUNSUP above),
+ * which sizes the workspace and changes no result.  Exact integers (integer atomics only): independent of launch geometry
+ * and of chunk, identical from run to run.  workspace: a 256-byte aligned device buffer of at least
+ * ffm_eval_boot_ws_bytes(N, chunk) bytes (the library allocates nothing); null pointers, N, B or chunk <= 0,
+ * G > FFM_MAX_GROUPS, a misaligned or short workspace: FFM_EINVAL, nothing launched.
+ */
+int64_t ffm_eval_boot_ws_bytes(int N, int chunk);
+int ffm_eval_boot_counts(const float* prob, const int64_t* label, const int64_t* attr, int N, int G, int B, int chunk,
+                         int64_t seed, int tag, uint64_t* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * Logits heads with a transport plan, TRAINER.GLP_OT.OT = 'Sinkhorn' (mode 1) / 'COT' (mode 2)

@@ -12,6 +12,7 @@ object with images/s of both, every pass's milliseconds, and torch.cuda.memory_a
 
     python tools/bench_eval.py [--batches 4] [--pairs 3] [--no-memory]
     python tools/bench_eval.py --leg forward|infer      one leg only (for a rocprofv3 --kernel-trace --stats run)
+    python tools/bench_eval.py --bootstrap 1000         also the time TEST.BOOTSTRAP = 1000 adds to one test() ("bootstrap")
     python tools/bench_eval.py --stats <kernel_stats.csv> [...]   c_fc time per call from such runs (no GPU work):
                                                         the GEMM kernels whose epilogue flags hold FFM_EPI_GELU
 """
@@ -57,6 +58,8 @@ def main():
     ap.add_argument("--leg", choices=["both", "forward", "infer"], default="both")
     ap.add_argument("--no-memory", action="store_true")
     ap.add_argument("--stats", nargs="+")
+    ap.add_argument("--bootstrap", type=int, default=0,
+                    help="also report what TEST.BOOTSTRAP = B adds to one test(): the replicate tables and their scoring")
     a = ap.parse_args()
     if a.stats:
         print(json.dumps({"c_fc_kernels": c_fc_stats(a.stats)}))
@@ -117,6 +120,28 @@ def main():
         res[f"{n}_images_per_sec"] = round(images / best * 1e3, 1)
     if a.leg == "both":
         res["speedup"] = round(min(ms["forward"]) / min(ms["infer"]), 4)
+    if a.bootstrap > 0:
+        # what TEST.BOOTSTRAP adds to one test(): the replicate tables of every attribute column with their one D2H copy
+        # (GPU events), and the host's scoring of them (wall time)
+        import time
+        from fairfedmed_amd import metrics as M
+        with eng.inference():
+            prob = torch.cat([torch.softmax(eng.infer(img, attr), -1) for img, attr, _, _ in batches]).float().contiguous()
+        y = torch.cat([b[2] for b in batches]).contiguous()
+        at = torch.cat([b[3] for b in batches], dim=1)
+        tables = ref[names[-1]].cpu().numpy()
+
+        def boot():
+            return torch.stack([ops.eval_boot_counts(prob, y, at[k].contiguous(), 8, a.bootstrap, 0, tag=1)
+                                for k in range(at.shape[0])]).cpu().numpy()
+
+        boot()
+        runs = [timed(boot) for _ in range(a.pairs)]
+        t0 = time.perf_counter()
+        ci = M.bootstrap_intervals(tables, runs[-1][1])
+        res["bootstrap"] = {"replicates": a.bootstrap, "samples": images, "attribute_columns": int(at.shape[0]),
+                            "tables_ms": [round(t, 3) for t, _ in runs],
+                            "intervals_host_ms": round((time.perf_counter() - t0) * 1e3, 3), "degenerate": ci["degenerate"]}
     if not a.no_memory and a.leg == "both":
         res["workspace_bytes"] = eng.infer_ws.nbytes()
         import gc
