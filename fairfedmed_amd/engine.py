@@ -298,6 +298,9 @@ class _Block:
         return self.packed[name] if self.packed else None
 
 
+_TTS = Tuple[Optional[Tensor], Optional[Tensor]]
+
+
 @dataclass
 class _LayerBufs:
     """What one residual block of `_stack_forward` reads and writes, cut to the rows in use.  Two providers: `_Stack.layer`
@@ -318,14 +321,12 @@ class _LayerBufs:
     rowp: Optional[Tensor] = None              # partial row sums of x (ln_1 folded into qkv), of x_out, of xm (ln_2 into c_fc)
     rowp_out: Optional[Tensor] = None
     rowp2: Optional[Tensor] = None
-    t1: Optional[Tensor] = None                # rank vectors of c_fc / c_proj: outputs of the fused route (optional there),
-    ts1: Optional[Tensor] = None               # operands of the rank > 16 route
-    t2: Optional[Tensor] = None
-    ts2: Optional[Tensor] = None
-    t3: Optional[Tensor] = None                # ... of attn.in_proj / attn.out_proj (a tower with attention sites)
-    ts3: Optional[Tensor] = None
-    t4: Optional[Tensor] = None
-    ts4: Optional[Tensor] = None
+    # rank vectors (t, ts) of the block's four linears, where they carry a site: outputs of the fused route (optional
+    # there), operands of the rank > 16 route
+    in_proj: _TTS = (None, None)
+    out_proj: _TTS = (None, None)
+    c_fc: _TTS = (None, None)
+    c_proj: _TTS = (None, None)
 
 
 class _Stack:
@@ -421,13 +422,13 @@ class _Stack:
         fc, proj = self.sites[i] if self.sites else (None, None)
         ain, aout = self.asites[i] if self.asites else (None, None)
         h = self.h_l[i] if self.asites else self.h
+        tts = lambda s: (s.t, s.ts) if s else (None, None)
         return _LayerBufs(self.x[i][:rows], self.xm[i][:rows], self.qkv[i][:rows], self.o[i][:rows], h[:rows],
                           self.h2[i][:rows], self.pre[i][:rows], self.act[i][:rows], self.x[i + 1][:rows], self.lse[i],
                           self.st1[i], self.st2[i], self.rowp[i] if self.rowp is not None else None,
                           self.rowp[i + 1] if self.rowp is not None else None,
                           self.rowp2[i] if self.rowp2 is not None else None,
-                          fc and fc.t, fc and fc.ts, proj and proj.t, proj and proj.ts,
-                          ain and ain.t, ain and ain.ts, aout and aout.t, aout and aout.ts)
+                          in_proj=tts(ain), out_proj=tts(aout), c_fc=tts(fc), c_proj=tts(proj))
 
 
 class _InferWorkspace:
@@ -477,11 +478,10 @@ class _InferWorkspace:
 
     def layer(self, i: int, rows: int) -> _LayerBufs:
         a, b = self.xs[i & 1], self.xs[(i + 1) & 1]
-        rp = self.rowps
+        rp, tts = self.rowps, (self.t, self.ts)
         return _LayerBufs(a[:rows], self.xm[:rows], self.qkv[:rows], self.o[:rows], self.h[:rows], self.h2[:rows], None,
                           self.act[:rows], b[:rows], rowp=rp[i & 1] if rp else None, rowp_out=rp[(i + 1) & 1] if rp else None,
-                          rowp2=self.rowp2, t1=self.t, ts1=self.ts, t2=self.t, ts2=self.ts, t3=self.t, ts3=self.ts,
-                          t4=self.t, ts4=self.ts)
+                          rowp2=self.rowp2, in_proj=tts, out_proj=tts, c_fc=tts, c_proj=tts)
 
     def nbytes(self) -> int:
         """Bytes of device memory the workspace holds."""
@@ -492,6 +492,22 @@ class _InferWorkspace:
                     seen.add(t.data_ptr())
                     n += t.numel() * t.element_size()
         return n
+
+
+def _site_fwd(site: Optional[LoraSite], gemm, x, W, out, attr, rps, tts=None, ln=False, **k) -> None:
+    """A linear of a block that may carry no site: the plain product, or the site's (LoraSite.fwd)."""
+    if site is None:
+        gemm(x, W, out, **k)
+    else:
+        site.fwd(x, W, out, attr, rps, gemm=gemm, tts=tts, ln=ln, **k)
+
+
+def _site_bwd(site: Optional[LoraSite], gemm, g, Wt, dx, attr, rps, lgrad=None, down=True, **k) -> None:
+    """... and its dX product (LoraSite.bwd)."""
+    if site is None:
+        gemm(g, Wt, dx, **k)
+    else:
+        site.bwd(g, Wt, dx, attr, rps, gemm=gemm, lgrad=lgrad, down=down, **k)
 
 
 class FairLoRAEngine:
@@ -828,81 +844,50 @@ class FairLoRAEngine:
         """The tower input is in layer 0's `x`; returns the tower output view.  bufs: the provider of every block's
         `_LayerBufs` - the tower's own stash (default: training and forward()) or an `_InferWorkspace`, whose sets have no
         pre-activation, no rank vectors and no statistics: the same launches in the same order, fewer stores."""
-        r = st.rank
         gemm = st.gemm
         bufs = st if bufs is None else bufs
-        out = lb = None
+        out = lb = sfc = None
         rt = st.route(rows)
         fold, fold2 = rt.ln1, rt.ln2
+
+        def lin(site, a, w, y, tts, **k):
+            _site_fwd(site, gemm, a, w, y, attr, rows_per_sample, tts=tts, **k)
 
         def fc(a, w, **k):
             # c_fc + QuickGELU of the current block: pre-activation and activation (the backward reads both), or the
             # activation alone
             if lb.pre is None:
-                gemm(a, w, lb.act, gelu_only=True, **k)
+                lin(sfc, a, w, lb.act, lb.c_fc, gelu_only=True, **k)
             else:
-                gemm(a, w, lb.pre, gelu_out=lb.act, **k)
+                lin(sfc, a, w, lb.pre, lb.c_fc, gelu_out=lb.act, **k)
         for i, blk in enumerate(st.blocks):
             lb = bufs.layer(i, rows)
             x, xm, qkv, o, h, h2, act = lb.x, lb.xm, lb.qkv, lb.o, lb.h, lb.h2, lb.act
-            if st.asites:
-                # adapters on the attention projections: the packed in-projection (before q is scaled: the attention
-                # kernels scale) and the out-projection, a c_proj-type product with the residual (and ln_2's row sums)
-                ain, aout = st.asites[i]
-                if self.fused_rank:
-                    ro = ain.rank_fwd(attr, rows_per_sample, lb.t3, lb.ts3, ln=bool(fold))
-                    if fold:
-                        ln = ops.LnIn(lb.rowp, 1 if i == 0 else fold, blk.c_in, lb.st1[0], lb.st1[1], rk=ain.lnrk)
-                        gemm(x, blk.w_in_ln, qkv, bias=blk.d_in, lw=ain.B, rankop=ro, b_packed=blk.pk("w_in_ln"), ln_in=ln)
-                    else:
-                        ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
-                        gemm(h, blk.w_in, qkv, bias=blk.b_in, lw=ain.B, rankop=ro, b_packed=blk.pk("w_in"))
-                else:
-                    ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
-                    ain.down_fwd(h, attr, rows_per_sample, lb.t3, lb.ts3)
-                    gemm(h, blk.w_in, qkv, bias=blk.b_in, ts=lb.ts3, lw=ain.B)
-                ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
-                if self.fused_rank:
-                    gemm(o, blk.w_out, xm, bias=blk.b_out, lw=aout.B, res=x, b_packed=blk.pk("w_out"),
-                         rankop=aout.rank_fwd(attr, rows_per_sample, lb.t4, lb.ts4), rowstats=lb.rowp2 if fold2 else None)
-                else:
-                    aout.down_fwd(o, attr, rows_per_sample, lb.t4, lb.ts4)
-                    gemm(o, blk.w_out, xm, bias=blk.b_out, ts=lb.ts4, lw=aout.B, res=x)
-            elif fold:
+            # the block's four linears, each with its site or None (attention sites alone: plain c_fc / c_proj)
+            ain, aout = st.asites[i] if st.asites else (None, None)
+            sfc, sproj = st.sites[i] if st.sites else (None, None)
+            if fold:
                 # ln_1 rides inside the qkv product: raw rows x gamma-scaled weight, normalised in the epilogue with the
                 # row sums the producer of x left behind (block 0: embed_lnpre, else the previous block's c_proj)
-                ln = ops.LnIn(lb.rowp, 1 if i == 0 else fold, blk.c_in, lb.st1[0], lb.st1[1])
-                gemm(x, blk.w_in_ln, qkv, bias=blk.d_in, b_packed=blk.pk("w_in_ln"), ln_in=ln)
+                ln = ops.LnIn(lb.rowp, 1 if i == 0 else fold, blk.c_in, lb.st1[0], lb.st1[1], rk=ain and ain.lnrk)
+                lin(ain, x, blk.w_in_ln, qkv, lb.in_proj, ln=True, bias=blk.d_in, b_packed=blk.pk("w_in_ln"), ln_in=ln)
             else:
                 ops.layernorm_fwd(x, h, blk.ln1_w, blk.ln1_b, lb.st1[0], lb.st1[1])
-                gemm(h, blk.w_in, qkv, bias=blk.b_in, b_packed=blk.pk("w_in"))
-            if not st.asites:
-                ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
-                gemm(o, blk.w_out, xm, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"), rowstats=lb.rowp2 if fold2 else None)
-            if not fold2:
-                ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, lb.st2[0], lb.st2[1])
-            r = st.rank if st.sites else 0            # (a tower with attention sites alone: plain c_fc / c_proj)
-            sfc, sproj = st.sites[i] if r else (None, None)
-            if r and self.fused_rank:
-                ro = sfc.rank_fwd(attr, rows_per_sample, lb.t1, lb.ts1, ln=bool(fold2))
-                if fold2:
-                    # ln_2 rides inside the c_fc product (h2 is never written; dA(c_fc) takes the raw rows, _stack_backward)
-                    ln = ops.LnIn(lb.rowp2, fold2, blk.c_fc, lb.st2[0], lb.st2[1], rk=sfc.lnrk)
-                    fc(xm, blk.w_fc_ln, bias=blk.d_fc, lw=sfc.B, rankop=ro, b_packed=blk.pk("w_fc_ln"), ln_in=ln)
-                else:
-                    fc(h2, blk.w_fc, bias=blk.b_fc, lw=sfc.B, rankop=ro, b_packed=blk.pk("w_fc"))
-                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, lw=sproj.B, res=xm,
-                     rankop=sproj.rank_fwd(attr, rows_per_sample, lb.t2, lb.ts2), b_packed=blk.pk("w_proj"),
-                     rowstats=lb.rowp_out if (fold and i + 1 < st.layers) else None)
-            elif r:
-                sfc.down_fwd(h2, attr, rows_per_sample, lb.t1, lb.ts1)
-                fc(h2, blk.w_fc, bias=blk.b_fc, ts=lb.ts1, lw=sfc.B)
-                sproj.down_fwd(act, attr, rows_per_sample, lb.t2, lb.ts2)
-                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, ts=lb.ts2, lw=sproj.B, res=xm)
+                lin(ain, h, blk.w_in, qkv, lb.in_proj, bias=blk.b_in, b_packed=blk.pk("w_in"))
+            # (an adapted in-projection is the packed one, before q is scaled: the attention kernels scale)
+            ops.attention_fwd(qkv, o, lb.lse, images, st.L, st.heads, st.causal)
+            # the out-projection: a c_proj-type product with the residual (and, ln_2 folded, its row sums)
+            lin(aout, o, blk.w_out, xm, lb.out_proj, bias=blk.b_out, res=x, b_packed=blk.pk("w_out"),
+                rowstats=lb.rowp2 if fold2 else None)
+            if fold2:
+                # ln_2 rides inside the c_fc product (h2 is never written; dA(c_fc) takes the raw rows, _stack_backward)
+                ln = ops.LnIn(lb.rowp2, fold2, blk.c_fc, lb.st2[0], lb.st2[1], rk=sfc.lnrk)
+                fc(xm, blk.w_fc_ln, ln=True, bias=blk.d_fc, b_packed=blk.pk("w_fc_ln"), ln_in=ln)
             else:
+                ops.layernorm_fwd(xm, h2, blk.ln2_w, blk.ln2_b, lb.st2[0], lb.st2[1])
                 fc(h2, blk.w_fc, bias=blk.b_fc, b_packed=blk.pk("w_fc"))
-                gemm(act, blk.w_proj, lb.x_out, bias=blk.b_proj, res=xm, b_packed=blk.pk("w_proj"),
-                     rowstats=lb.rowp_out if (fold and i + 1 < st.layers) else None)
+            lin(sproj, act, blk.w_proj, lb.x_out, lb.c_proj, bias=blk.b_proj, res=xm, b_packed=blk.pk("w_proj"),
+                rowstats=lb.rowp_out if (fold and i + 1 < st.layers) else None)
             out = lb.x_out
         return out
 
@@ -914,19 +899,25 @@ class FairLoRAEngine:
         r = st.rank if st.sites else 0                # (attention sites alone: the MLP's backward is the plain one)
         att = bool(st.asites)
         gemm = st.gemm
-        g, g1 = st.g[:rows], st.g1[:rows]
+        g, do, dh = st.g[:rows], st.do[:rows], st.dh[:rows]
         main = torch.cuda.current_stream(self.device)
         rt = st.route(rows)
+
+        def dX(site, gy, wt, dx, **k):
+            _site_bwd(site, gemm, gy, wt, dx, attr, rows_per_sample, **k)
         for i in range(st.layers - 1, -1, -1):
             blk = st.blocks[i]
-            x, xm = st.x[i][:rows], st.xm[i][:rows]
+            x, xm, qkv, o = st.x[i][:rows], st.xm[i][:rows], st.qkv[i][:rows], st.o[i][:rows]
             pre, act, h2 = st.pre[i][:rows], st.act[i][:rows], st.h2[i][:rows]
             # the dX chain ends inside block 0: behind dX(c_proj) - or, with attention sites, behind the attention backward
             # (last_att: block 0 runs its MLP part as every other block does and stops at dqkv)
             last_att = att and (i == 0) and not need_input_grad
             last = (i == 0) and not need_input_grad and not att
-            if att:
-                g1 = st.g1_l[i][:rows]                # dL/d x_mid, kept per layer: dB(out_proj) reads it on the side stream
+            # attention sites: their reductions read dL/d x_mid (dB of out_proj), dqkv (dB of in_proj) and ln_1's output
+            # (dA of in_proj) on the side stream - kept per layer, shared by all blocks in a tower without them
+            ain, aout = st.asites[i] if att else (None, None)
+            g1, dqkv, h = ((st.g1_l[i], st.dqkv_l[i], st.h_l[i]) if att else (st.g1, st.dqkv, st.h))
+            g1, dqkv, h = g1[:rows], dqkv[:rows], h[:rows]
             if r:
                 # gradient w.r.t. this block's output lives in its own buffer (read later by the side stream)
                 gi, dpre = st.g_l[i][:rows], st.dpre_l[i][:rows]
@@ -934,7 +925,6 @@ class FairLoRAEngine:
                     self._glue(lambda gi=gi, g=g: gi.copy_(g))
                 sfc, sproj = st.sites[i]
                 # ---- critical path: u = g B^T and dX (+ LoRA dx term), dS partials
-                fused = self.fused_rank
                 if last:
                     # the step's tail: dB(c_proj) needs only gi and the forward's ts2 - it starts beside this block's dX
                     # product instead of behind it
@@ -948,22 +938,18 @@ class FairLoRAEngine:
                 lg = rt.lgrad
                 # ln_2's backward rides in this block's two dX products (not block 0 of a tower that stops there)
                 lnb = 0 if last else rt.ln2_bwd
-                if fused:
-                    ro = sproj.rank_bwd(attr, rows_per_sample, rows, lgrad=(sfc.ts[:rows], sfc.pB, sproj.pA) if lg else None)
-                    gemm(gi, blk.w_proj_t, dpre, lw=sproj.A, lw_is_kr=True, dgelu_aux=pre, rankop=ro,
-                         b_packed=blk.pk("w_proj_t"), lnb_stat=ops.LnBwdStat(st.lnb_part) if lnb else None)
-                else:
-                    sproj.down_bwd(gi, attr, rows_per_sample)
-                    gemm(gi, blk.w_proj_t, dpre, ts=sproj.us[:rows], lw=sproj.A, lw_is_kr=True, dgelu_aux=pre)
-                if fused and not last:
-                    # u1 = dpre B_fc^T rides inside the dX GEMM of c_fc
-                    ro = sfc.rank_bwd(attr, rows_per_sample, rows)
-                    if lnb:
-                        # ... and stores dL/d x_mid = LayerNorm backward(g_h) + gi directly: no ffm_layernorm_bwd launch
-                        gemm(dpre, blk.w_fc_t, g1, lw=sfc.A, lw_is_kr=True, rankop=ro, b_packed=blk.pk("w_fc_t"),
-                             lnb_apply=ops.LnBwdApply(st.lnb_part, lnb, xm, blk.ln2_w, st.st2[i][0], st.st2[i][1], sfc.lnrk, gi))
-                    else:
-                        gemm(dpre, blk.w_fc_t, st.dh[:rows], lw=sfc.A, lw_is_kr=True, rankop=ro, b_packed=blk.pk("w_fc_t"))
+                dX(sproj, gi, blk.w_proj_t, dpre, lgrad=(sfc.ts[:rows], sfc.pB, sproj.pA) if lg else None, dgelu_aux=pre,
+                   b_packed=blk.pk("w_proj_t"), lnb_stat=ops.LnBwdStat(st.lnb_part) if lnb else None)
+
+                def dx_fc(down=True):
+                    # dX(c_fc); lnb: it stores dL/d x_mid = LayerNorm backward(g_h) + gi directly - no ffm_layernorm_bwd launch
+                    la = ops.LnBwdApply(st.lnb_part, lnb, xm, blk.ln2_w, st.st2[i][0], st.st2[i][1], sfc.lnrk, gi) if lnb else None
+                    dX(sfc, dpre, blk.w_fc_t, g1 if lnb else dh, down=down, b_packed=blk.pk("w_fc_t"), lnb_apply=la)
+                # c_fc's down projection u1 = dpre B_fc^T rides inside its dX product, or stands alone in front of it: where
+                # the chain ends with it, and at rank > 16, where the reductions may start behind it, beside the product
+                alone = last or not self.fused_rank
+                if not alone:
+                    dx_fc()
                 else:
                     if last:
                         # the dX chain ends with this down projection: the three reductions that do not need its result
@@ -1004,38 +990,54 @@ class FairLoRAEngine:
                     reductions()
                 if last:
                     break
-                if not fused:
-                    gemm(dpre, blk.w_fc_t, st.dh[:rows], ts=sfc.us[:rows], lw=sfc.A, lw_is_kr=True)
+                if alone:
+                    dx_fc(down=False)
                 gout = st.g_l[i - 1][:rows] if i > 0 else g
             else:
+                # (no MLP sites: the two plain products, from the weights as loaded)
                 gi, dpre, gout = g, st.dpre[:rows], g
                 lnb = red_at = 0
                 gemm(gi, blk.w_proj_t, dpre, dgelu_aux=pre)
-                gemm(dpre, blk.w_fc_t, st.dh[:rows])
+                gemm(dpre, blk.w_fc_t, dh)
             if not lnb:
-                ops.layernorm_bwd(st.dh[:rows], xm, blk.ln2_w, st.st2[i][0], st.st2[i][1], gi, g1)
-            if att:
-                self._attn_sites_backward(st, i, rows, images, attr, rows_per_sample, g1, gout, last_att, red_at, reductions if r else None)
-                if last_att:
-                    break
-                continue
-            gemm(g1, blk.w_out_t, st.do[:rows], b_packed=blk.pk("w_out_t"))
+                ops.layernorm_bwd(dh, xm, blk.ln2_w, st.st2[i][0], st.st2[i][1], gi, g1)
+            # ---- the attention half
+            dX(aout, g1, blk.w_out_t, do, b_packed=blk.pk("w_out_t"))
             # ln_1's backward: its two row sums leave with the attention backward (two partial rows per head), and the dX
-            # product of the in-projection stores dL/d x = LayerNorm backward(g_h) + g1 directly
+            # product of the in-projection stores dL/d x = LayerNorm backward(g_h) + g1 directly (never with an adapted
+            # in-projection: tower_route keeps the fold off there, and ffm_layernorm_bwd runs)
             lnb1 = rt.ln1_bwd
-            ops.attention_bwd(st.qkv[i][:rows], st.o[i][:rows], st.do[:rows], st.lse[i], st.delta, st.dqkv[:rows],
-                              images, st.L, st.heads, st.causal,
+            ops.attention_bwd(qkv, o, do, st.lse[i], st.delta, dqkv, images, st.L, st.heads, st.causal,
                               ln_stat=(blk.c_in, blk.d_in, st.lnb_part) if lnb1 else None)
             if red_at == 1:
                 reductions()
-            if lnb1:
-                gemm(st.dqkv[:rows], blk.w_in_t, gout, b_packed=blk.pk("w_in_t"),
-                     lnb_apply=ops.LnBwdApply(st.lnb_part, lnb1, x, blk.ln1_w, st.st1[i][0], st.st1[i][1], None, g1))
+            if last_att:
+                # the chain ends at dqkv: the in-projection takes the stand-alone down projection for us and the dS partials,
+                # as block 0's c_fc does in a tower without attention sites
+                ain.down_bwd(dqkv, attr, rows_per_sample)
             else:
-                gemm(st.dqkv[:rows], blk.w_in_t, st.dh[:rows], b_packed=blk.pk("w_in_t"))
-                ops.layernorm_bwd(st.dh[:rows], x, blk.ln1_w, st.st1[i][0], st.st1[i][1], g1, gout)
+                la = ops.LnBwdApply(st.lnb_part, lnb1, x, blk.ln1_w, st.st1[i][0], st.st1[i][1], None, g1) if lnb1 else None
+                dX(ain, dqkv, blk.w_in_t, gout if lnb1 else dh, b_packed=blk.pk("w_in_t"), lnb_apply=la)
+                if not lnb1:
+                    ops.layernorm_bwd(dh, x, blk.ln1_w, st.st1[i][0], st.st1[i][1], g1, gout)
             if red_at == 2:
                 reductions()
+            if att:
+                # the attention sites' four reductions: everything they read is the block's own (g1_l, dqkv_l, o, h_l or the
+                # raw rows x; us and the partials in the sites), so they trail the chain on the side stream behind one event
+                self._ev_record(self.ev_attn[i], main)
+                self._ev_wait(self.grad_stream, self.ev_attn[i])
+                with self._on(self.grad_stream):
+                    aout.grad_B(g1)
+                    aout.grad_A(o)
+                    ain.grad_B(dqkv)
+                    if rt.ln1:
+                        ain.grad_A(x, ln_stats=st.st1[i])     # ln_1 was folded into the qkv product: dA from the raw rows
+                    else:
+                        ain.grad_A(h)
+                    self._reduce_plan(st, rows, not last_att, i, attn=True).run()
+            if last_att:
+                break
         if r or att:
             if self.sops.glob:
                 self._glue(self.sops.finish, self.grad_stream)     # dS_eff -> dS, dS_global
@@ -1043,72 +1045,20 @@ class FairLoRAEngine:
             self._ev_wait(main, self.ev_grads)
         return g
 
-    def _attn_sites_backward(self, st: _Stack, i: int, rows: int, images: int, attr: Optional[Tensor], rps: int,
-                             g1: Tensor, gout: Tensor, last: bool, red_at: int, mlp_reductions) -> None:
-        """Block i's attention part of the backward pass where attn.in_proj / attn.out_proj carry adapters: dX(out_proj)
-        with the adapter's dx term, the attention backward, dX(in_proj) likewise and ln_1's backward as its own kernel
-        (tower_route keeps ln_1's backward fold off here).  last: the chain ends at dqkv - the in-projection takes the
-        stand-alone down projection for us and the dS partials, as block 0's c_fc does in a tower without these sites.
-        Everything the four reductions read is the block's own (g1_l, dqkv_l, o, h_l or the raw rows x; us and the partials
-        in the sites), so they trail the chain on the side stream behind one event and no buffer waits for them."""
-        blk, gemm, main = st.blocks[i], st.gemm, torch.cuda.current_stream(self.device)
-        ain, aout = st.asites[i]
-        x, o, dqkv, do, dh = st.x[i][:rows], st.o[i][:rows], st.dqkv_l[i][:rows], st.do[:rows], st.dh[:rows]
-        rt = st.route(rows)
-        if self.fused_rank:
-            gemm(g1, blk.w_out_t, do, lw=aout.A, lw_is_kr=True, rankop=aout.rank_bwd(attr, rps, rows), b_packed=blk.pk("w_out_t"))
-        else:
-            aout.down_bwd(g1, attr, rps)
-            gemm(g1, blk.w_out_t, do, ts=aout.us[:rows], lw=aout.A, lw_is_kr=True)
-        ops.attention_bwd(st.qkv[i][:rows], o, do, st.lse[i], st.delta, dqkv, images, st.L, st.heads, st.causal)
-        if red_at == 1 and mlp_reductions is not None:
-            mlp_reductions()
-        if last or not self.fused_rank:
-            ain.down_bwd(dqkv, attr, rps)
-        if not last:
-            if self.fused_rank:
-                gemm(dqkv, blk.w_in_t, dh, lw=ain.A, lw_is_kr=True, rankop=ain.rank_bwd(attr, rps, rows), b_packed=blk.pk("w_in_t"))
-            else:
-                gemm(dqkv, blk.w_in_t, dh, ts=ain.us[:rows], lw=ain.A, lw_is_kr=True)
-            ops.layernorm_bwd(dh, x, blk.ln1_w, st.st1[i][0], st.st1[i][1], g1, gout)
-        if red_at == 2 and mlp_reductions is not None:
-            mlp_reductions()
-        ev = self.ev_attn[i]
-        self._ev_record(ev, main)
-        self._ev_wait(self.grad_stream, ev)
-        with self._on(self.grad_stream):
-            aout.grad_B(g1)
-            aout.grad_A(o)
-            ain.grad_B(dqkv)
-            if rt.ln1:
-                ain.grad_A(x, ln_stats=st.st1[i])         # ln_1 was folded into the qkv product: dA from the raw rows
-            else:
-                ain.grad_A(st.h_l[i][:rows])
-            self._attn_reduce_plan(st, rows, not last, i).run()
-
-    def _attn_reduce_plan(self, st: _Stack, rows: int, in_gemm: bool, layer: int):
-        """As _reduce_plan, for the block's attention sites.  in_gemm: dX(in_proj) ran and left the in-projection's dS
-        partials (False: the stand-alone down projection did)."""
-        key = (rows, in_gemm, layer, "attn")
+    def _reduce_plan(self, st: _Stack, rows: int, full_bwd: bool, layer: int, attn: bool = False):
+        """Descriptor table (built once per row count and block) that sums into params.grad the partials of the block's MLP
+        sites (c_fc, c_proj) or - attn - of its attention sites (in_proj, out_proj).  full_bwd: the dX chain runs through
+        block 0's first site too (False: it ends in front of that site's dX product)."""
+        key = (rows, full_bwd, layer) + (("attn",) if attn else ())
         if key not in st.plans:
-            (ain, aout), pk = st.asites[layer], st.blocks[layer].packed is not None
-            ob, oa, os_ = aout.reduce_entries(rows, aout.ds_rows(rows, pk))
-            ib, ia, is_ = ain.reduce_entries(rows, ain.ds_rows(rows, pk, gemm=in_gemm))
-            st.plans[key] = ops.ReducePlan([os_, is_, ob, oa, ib, ia], self.device)
-        return st.plans[key]
-
-    def _reduce_plan(self, st: _Stack, rows: int, full_bwd: bool, layer: int):
-        """Descriptor table (built once per row count and block) that sums the block's partials into params.grad."""
-        key = (rows, full_bwd, layer)
-        if key not in st.plans:
-            (fc, proj), pk = st.sites[layer], st.blocks[layer].packed is not None
+            (a, b), pk = (st.asites if attn else st.sites)[layer], st.blocks[layer].packed is not None
             # (FFM_EPI_LGRAD: dA(c_proj) and dB(c_fc) hold one partial per row tile of the dX product of c_proj)
-            nlg = st.route(rows).lgrad or None
+            nlg = None if attn else (st.route(rows).lgrad or None)
             # dS partial rows: those of the dX product that carries the down projection (c_proj's also the dGELU); block 0's
-            # c_fc has no dX product where the chain ends there, and takes the stand-alone kernel
-            pb, pa, ps = proj.reduce_entries(rows, proj.ds_rows(rows, pk, dgelu=True), splits_A=nlg)
-            fb, fa, fs = fc.reduce_entries(rows, fc.ds_rows(rows, pk, gemm=layer > 0 or full_bwd), splits_B=nlg)
-            st.plans[key] = ops.ReducePlan([ps, fs, pb, pa, fb, fa], self.device)
+            # first site has no dX product where the chain ends there, and takes the stand-alone kernel
+            bb, ba, bs = b.reduce_entries(rows, b.ds_rows(rows, pk, dgelu=not attn), splits_A=nlg)
+            ab, aa, as_ = a.reduce_entries(rows, a.ds_rows(rows, pk, gemm=layer > 0 or full_bwd), splits_B=nlg)
+            st.plans[key] = ops.ReducePlan([bs, as_, bb, ba, ab, aa], self.device)
         return st.plans[key]
 
     # ------------------------------------------------------------ replay --

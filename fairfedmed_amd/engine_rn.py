@@ -28,8 +28,11 @@ Tensor = torch.Tensor
 
 
 class _Lora(LoraSite):
-    """A site of the RN50 tower: it sizes its own dS partials, joins the engine's pack table, and wraps the product
-    (fwd / bwd) and its two reductions (grads) around the site's operands."""
+    """A site of the RN50 tower: it sizes its own dS partials, joins the engine's pack table and runs its two reductions
+    together (grads).  Its products are LoraSite.fwd / bwd; what they take here beside bias / res: colstats (forward) -
+    the GEMM also leaves the column sums of its row tiles there, for the BatchNorm that follows; bnbwd with colstats
+    (backward, fused sites only) - dx is the gradient of a BatchNorm output, and the product's epilogue leaves that
+    BatchNorm's backward column sums in colstats (ops.gemm_nt)."""
 
     def __init__(self, eng: "RN50Engine", prefix: str, K: int, N: int, max_rows: int, fair: bool):
         super().__init__(eng, prefix, K, N, max_rows, fair)
@@ -40,31 +43,6 @@ class _Lora(LoraSite):
             eng.pack_entries += self.pack_entries()
         if fair:
             self.alloc_ds(nb * lo.num_groups * lo.rank)
-
-    def fwd(self, x: Tensor, W: Tensor, out: Tensor, attr: Optional[Tensor], rps: int, bias=None, res=None,
-            colstats: Optional[Tensor] = None) -> None:
-        """colstats: the GEMM also leaves the column sums of its row tiles there (the BatchNorm that follows)."""
-        rows = x.shape[0]
-        t, ts = self.t[:rows], self.ts[:rows]
-        if self.fused:
-            ops.gemm_nt(x, W, out, bias=bias, lw=self.B, res=res, rankop=self.rank_fwd(attr, rps, t, ts), colstats=colstats)
-            return
-        self.down_fwd(x, attr, rps, t, ts)
-        ops.gemm_nt(x, W, out, bias=bias, ts=ts, lw=self.B, res=res, colstats=colstats)
-
-    def bwd(self, g: Tensor, Wt: Tensor, dx: Tensor, attr: Optional[Tensor], rps: int, res=None,
-            bnbwd=None, colstats: Optional[Tensor] = None) -> None:
-        """g = dL/dy; writes dx = g W (+ LoRA term) (+ res) and the partial sums of dS; the caller runs grads() (dA, dB)
-        itself, on the gradient stream.  bnbwd / colstats (fused sites only): dx is the gradient of a BatchNorm
-        output, and the product's epilogue leaves that BatchNorm's backward column sums in colstats (ops.gemm_nt)."""
-        rows = g.shape[0]
-        if self.fused:
-            ops.gemm_nt(g, Wt, dx, lw=self.A, lw_is_kr=True, res=res, rankop=self.rank_bwd(attr, rps, rows), bnbwd=bnbwd,
-                        colstats=colstats)
-        else:
-            assert bnbwd is None
-            self.down_bwd(g, attr, rps)
-            ops.gemm_nt(g, Wt, dx, ts=self.us[:rows], lw=self.A, lw_is_kr=True, res=res)
 
     def grads(self, g: Tensor, x: Tensor) -> None:
         """The rank-r reductions dB = g^T ts, dA = x^T us (partials); nothing downstream of them in the dX chain."""

@@ -22,7 +22,8 @@ class LoraSite:
       ln        (gamma, beta) of a LayerNorm folded into the forward product: rkA_ln, its [2, 16] corrections lnrk;
       row1415   two vectors as rows 14 / 15 of rkB (rank <= 14): the dX product's t[14] / t[15] are the row sums against them.
     The towers pass in what differs: the rows to size for, a shared `u`, the floats of pS (alloc_ds), and the t / ts a
-    forward product writes (the evaluation pass keeps one pair for all layers)."""
+    forward product writes (the evaluation pass keeps one pair for all layers).  fwd / bwd are the adapted products of
+    both towers: the rank operands above around the caller's GEMM and its epilogue keywords."""
 
     def __init__(self, eng, prefix: str, K: int, N: int, max_rows: int, fair: bool = True, u: Optional[Tensor] = None,
                  wide: bool = False, ln: Optional[Tuple[Tensor, Tensor]] = None,
@@ -98,6 +99,38 @@ class LoraSite:
         S, attr, G, tail = self._tail(attr, rps)
         u, us, t = (b[:g.shape[0]] for b in (self.u, self.us, self.t))
         ops.lora_down(g, self.B, True, S, attr, self.rank, G, *tail, u, us, t if self.fair else None, self.pS)
+
+    # -- the adapted product: the down projection inside the GEMM, or in front of it ----------------------------
+    # what the rank > 16 arm hands its GEMM of the caller's epilogue keywords: the kernels that serve `ts=` take no
+    # packed weight, no LayerNorm fold and no BatchNorm-backward sums
+    _PLAIN = ("bias", "res", "gelu_out", "gelu_only", "dgelu_aux", "colstats")
+
+    def fwd(self, x: Tensor, W: Tensor, out: Tensor, attr: Optional[Tensor], rps: int, gemm=None,
+            tts: Optional[Tuple[Optional[Tensor], Optional[Tensor]]] = None, ln: bool = False, **k) -> None:
+        """out = x W^T + the adapter's term, through `gemm` (default: ops.gemm_nt, looked up at the call as every caller of
+        it does - the benchmark's timing wrapper replaces it; k: its epilogue keywords).
+        tts: the (t, ts) the product writes (default: the site's own); ln: x raw, its LayerNorm folded in (k: ln_in)."""
+        t, ts = (self.t[:x.shape[0]], self.ts[:x.shape[0]]) if tts is None else tts
+        gemm = gemm or ops.gemm_nt
+        if self.fused:
+            gemm(x, W, out, lw=self.B, rankop=self.rank_fwd(attr, rps, t, ts, ln=ln), **k)
+            return
+        self.down_fwd(x, attr, rps, t, ts)
+        gemm(x, W, out, ts=ts, lw=self.B, **{n: k[n] for n in self._PLAIN if n in k})
+
+    def bwd(self, g: Tensor, Wt: Tensor, dx: Tensor, attr: Optional[Tensor], rps: int, gemm=None,
+            lgrad: Optional[tuple] = None, down: bool = True, **k) -> None:
+        """g = dL/dy; writes dx = g W (+ the adapter's term) and us, the partial sums of dS; the caller runs the two
+        reductions (dA, dB) itself, on the gradient stream.  lgrad: ops.RankOp.lgrad.  down=False (rank > 16): the caller
+        has run down_bwd already, with launches of its own between the two."""
+        gemm = gemm or ops.gemm_nt
+        if self.fused:
+            gemm(g, Wt, dx, lw=self.A, lw_is_kr=True, rankop=self.rank_bwd(attr, rps, g.shape[0], lgrad), **k)
+            return
+        assert k.get("bnbwd") is None and lgrad is None
+        if down:
+            self.down_bwd(g, attr, rps)
+        gemm(g, Wt, dx, ts=self.us[:g.shape[0]], lw=self.A, lw_is_kr=True, **{n: k[n] for n in self._PLAIN if n in k})
 
     # -- the rank-r gradient reductions (partials) and their sum ------------------------------------------------
     def grad_B(self, g: Tensor) -> None:

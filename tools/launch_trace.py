@@ -27,7 +27,7 @@ def route_cfg():
     return dataclasses.replace(base, vision=dataclasses.replace(base.vision, layers=2), text=cfgs.vit_tiny().text)
 
 
-# case -> (config, dtype, max_images, images, mode); mode: train | infer (outside a session) | session (inside one)
+# case -> (config, dtype, max_images, images, mode[, environment]); mode: train | infer (outside a session) | session (inside one)
 CASES = {f"route_{d}_{n}": (route_cfg, d, 28, n, "train") for d, n in (("bf16", 13), ("bf16", 14), ("bf16", 28), ("f16", 28))}
 CASES.update({f"tiny_r{r}_{d}": ((lambda r=r: cfgs.vit_tiny(rank=r)), d, 3, 3, "train")
               for r, d in ((4, "f32"), (4, "bf16"), (24, "bf16"))})
@@ -42,9 +42,40 @@ for _m in ("infer", "session"):
     CASES[f"{_m}_tiny_r24"] = ((lambda: cfgs.vit_tiny(rank=24)), "bf16", 3, 3, _m)
 
 
-def record_case(mk_cfg, dtype, max_images, images, mode):
+def on(mk_cfg, targets):
+    """The same tower with its adapters on `targets` (LoraCfg.targets: 'attn' / 'mlp+attn')."""
+    def mk():
+        c = mk_cfg()
+        return dataclasses.replace(c, lora=dataclasses.replace(c.lora, targets=targets))
+    return mk
+
+
+# adapters on attn.in_proj / attn.out_proj too ("ma": mlp+attn) or alone ("a": attn)
+CASES.update({f"route_ma_bf16_{n}": (on(route_cfg, "mlp+attn"), "bf16", 28, n, "train") for n in (13, 28)})
+CASES["route_a_bf16_28"] = (on(route_cfg, "attn"), "bf16", 28, 28, "train")
+CASES.update({f"tiny_ma_r{r}_{d}": (on((lambda r=r: cfgs.vit_tiny(rank=r)), "mlp+attn"), d, 3, 3, "train")
+              for r, d in ((4, "f32"), (4, "bf16"), (24, "bf16"))})
+CASES["tiny_a_r24_bf16"] = (on(lambda: cfgs.vit_tiny(rank=24), "attn"), "bf16", 3, 3, "train")
+CASES["tiny_3d_ma"] = (on(cfgs.vit_tiny_3d, "mlp+attn"), "bf16", 6, 3, "train")
+# where a block's reductions start (FFM_RED_AT=1|2; by row count only the 19 700-row workload leaves 0), without and with
+# attention sites; a sixth element: environment switches for the engine's construction
+for _at in "12":
+    CASES[f"route_red{_at}_bf16_28"] = (route_cfg, "bf16", 28, 28, "train", {"FFM_RED_AT": _at})
+    CASES[f"route_ma_red{_at}_bf16_28"] = (on(route_cfg, "mlp+attn"), "bf16", 28, 28, "train", {"FFM_RED_AT": _at})
+for _m in ("infer", "session"):
+    CASES[f"{_m}_route_ma_28"] =(on(route_cfg, "mlp+attn"), "bf16", 28, 28, _m)
+    CASES[f"{_m}_tiny_ma_r24"] = (on(lambda: cfgs.vit_tiny(rank=24), "mlp+attn"), "bf16", 3, 3, _m)
+
+
+def record_case(mk_cfg, dtype, max_images, images, mode, env=None):
     mcfg = mk_cfg()
-    eng = create_engine(mcfg, synth.make_state_dict(mcfg, seed=1, lora_init="random"), dtype=DT[dtype], max_images=max_images)
+    old = {k: os.environ.get(k) for k in env or {}}
+    os.environ.update(env or {})                                # (the engine reads its switches when it is constructed)
+    try:
+        eng = create_engine(mcfg, synth.make_state_dict(mcfg, seed=1, lora_init="random"), dtype=DT[dtype], max_images=max_images)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
     eng.use_replay = False                                      # the engine must not record itself
     b = synth.make_batch(mcfg, images, seed=1234)
     img, attr, label = b["img"].cuda(), b["attrs"].t()[0].contiguous().cuda(), b["label"].cuda()
