@@ -10,6 +10,7 @@ file in TWIN_SOURCES is compiled twice - once as written (float32 + bfloat16, en
 with ``-DFFM_TWIN_F16`` (csrc/common.h: the file's 16-bit type becomes _Float16; every external symbol renamed
 ``<name>_f16``) - and a generated translation unit (csrc/_gen_dispatch.hip, from the prototypes of include/ffm_hip.h)
 defines the public entry points that take a ``dtype``: FFM_F16 goes to the half twin, everything else to the main object.
+A twin holds 16-bit kernels only: the storage-type dispatch of csrc/common.h (ffm_by_storage) names no float kernel there.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ LIB = os.path.join(CSRC, "libffm_hip.so")
 SOURCES = ["gemm.hip", "gemm_panel.hip", "gemm_panel_rk.hip", "gemm_panel_rk2.hip", "gemm_panel_rk3.hip", "gemm_skinny.hip", "rowwise.hip", "lora.hip", "head.hip", "head_ot.hip", "optim.hip", "dp.hip", "attention.hip", "attention3.hip", "attention_long.hip", "slice3d.hip", "conv.hip", "evalmetrics.hip", "evalsort.hip", "evalboot.hip", "transport.hip", "resize.hip", "text.hip", "switches.hip"]
 # files with 16-bit kernels behind a `dtype` argument (attention3.hip and attention_long.hip are templated on the storage types and need no
 # twin; switches.hip has no kernels: the one switch table, csrc/switches.h, that the main objects and the twins both read)
-TWIN_SOURCES = ["gemm.hip", "gemm_panel.hip", "gemm_panel_rk.hip", "gemm_panel_rk2.hip", "gemm_panel_rk3.hip", "gemm_skinny.hip", "rowwise.hip", "lora.hip", "head.hip", "head_ot.hip", "optim.hip", "attention.hip", "slice3d.hip", "conv.hip"]
+TWIN_SOURCES = ["gemm.hip", "gemm_panel.hip", "gemm_panel_rk.hip", "gemm_panel_rk2.hip", "gemm_panel_rk3.hip", "gemm_skinny.hip", "rowwise.hip", "lora.hip", "head.hip", "head_ot.hip", "attention.hip", "slice3d.hip", "conv.hip"]
 # C++-linkage names shared between those files (csrc/gemm_panel.h): renamed in the twins with the entry points
 TWIN_INTERNAL = ["ffm_panel", "ffm_panel_select", "ffm_panel_launch", "ffm_panel_launch_rk",
                  "ffm_panel_launch_rk2", "ffm_panel_launch_rk3", "ffm_skinny_ok", "ffm_skinny_launch"]

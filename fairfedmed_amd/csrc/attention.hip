@@ -43,8 +43,9 @@ template <> struct AT<bf16_t> {
 };
 template <> struct AT<float> {
     typedef f32x4 frag_t;
-    static constexpr int ES = 4, ROWB = 256, NCH = 16, ND = 4, CE = 4;
-    static constexpr int FPK = 1;
+    // ([[maybe_unused]]: the half twin of this file names no float kernel)
+    [[maybe_unused]] static constexpr int ES = 4, ROWB = 256, NCH = 16, ND = 4, CE = 4;
+    [[maybe_unused]] static constexpr int FPK = 1;
     static __device__ __forceinline__ frag_t pack(const f32x4* p, int s) { return p[s]; }
     static __device__ __forceinline__ frag_t tfrag(const float* xt, int ts, int d, int s, int g) {
         return *reinterpret_cast<const f32x4*>(xt + (size_t)d * ts + 16 * s + 4 * g);
@@ -1137,8 +1138,9 @@ extern "C" int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, 
         case ATTN_THIRD: return ffm_attn3_fwd(qkv, out, lse, B, L, heads, dtype, s);
         case ATTN_SECOND: return dispatch_fwd2(qkv, out, lse, B, L, heads, s);
         case ATTN_FIRST:
-            if (dtype == FFM_BF16) return dispatch_fwd<bf16_t>(nfp, qkv, out, lse, B, L, heads, causal, s);
-            return dispatch_fwd<float>(nfp, qkv, out, lse, B, L, heads, causal, s);
+            return ffm_by_storage(dtype, [&](auto tag) {
+                return dispatch_fwd<typename decltype(tag)::type>(nfp, qkv, out, lse, B, L, heads, causal, s);
+            });
         case ATTN_NONE: break;
     }
     return FFM_EINVAL;
@@ -1155,8 +1157,9 @@ extern "C" int ffm_attention_bwd(const void* qkv, const void* out, const void* d
         case ATTN_THIRD: return ffm_attn3_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, dtype, s, nullptr, nullptr, nullptr);
         case ATTN_SECOND: return dispatch_bwd2(qkv, out, dout, lse, delta, dqkv, B, L, heads, s);
         case ATTN_FIRST:
-            if (dtype == FFM_BF16) return dispatch_bwd<bf16_t>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
-            return dispatch_bwd<float>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
+            return ffm_by_storage(dtype, [&](auto tag) {
+                return dispatch_bwd<typename decltype(tag)::type>(nfp, qkv, out, dout, lse, delta, dqkv, B, L, heads, causal, s);
+            });
         case ATTN_NONE: break;
     }
     return FFM_EINVAL;

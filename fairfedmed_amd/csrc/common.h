@@ -49,6 +49,33 @@ template <typename F> int ffm_set_max_lds(F fn, int bytes) {
 }
 
 // ---------------------------------------------------------------------------
+// Storage-type dispatch.  A launcher picks its kernels' element type from a `dtype` code through ffm_by_storage and takes it
+// as a type tag in a generic lambda:
+//     return ffm_by_storage(dtype, [&](auto tag) { typedef typename decltype(tag)::type T; ...launch k<T>...; return FFM_OK; });
+// The lambda body is a template, so only the types named here are ever instantiated.  The half twin of a file is reached with
+// FFM_F16 alone (it reads as FFM_BF16 there), so a twin names the 16-bit type only and holds no float kernels.
+// ---------------------------------------------------------------------------
+template <typename T> struct ffm_type { typedef T type; };
+
+template <typename F> inline int ffm_by_storage(int dtype, F&& f) {
+    if (dtype == FFM_BF16) return f(ffm_type<bf16_t>{});
+#ifndef FFM_TWIN_F16
+    if (dtype == FFM_F32) return f(ffm_type<float>{});
+#endif
+    return FFM_EINVAL;
+}
+
+// The split-operand requests (float activations on the 16-bit matrix cores): the tag is the WEIGHT's storage type.  They
+// reach the main object only.
+template <typename F> inline int ffm_by_split_weight(int dtype, F&& f) {
+#ifndef FFM_TWIN_F16
+    if (dtype == FFM_F32_X3) return f(ffm_type<float>{});
+    if (dtype == FFM_F32_X3_W16) return f(ffm_type<f16_t>{});
+#endif
+    return FFM_EINVAL;
+}
+
+// ---------------------------------------------------------------------------
 // Element traits: T is float or bf16_t.  A "chunk" is 16 bytes of a row.
 // ---------------------------------------------------------------------------
 template <typename T> struct Elem;

@@ -17,7 +17,7 @@ template <> struct VecC<bf16_t> {
     static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) { Vec8<bf16_t>::store(p, v); }
 };
 template <> struct VecC<float> {
-    static constexpr int N = 4;
+    [[maybe_unused]] static constexpr int N = 4;          // (unused in the half twin, which holds no float kernel)
     static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(p);
         v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
@@ -648,9 +648,6 @@ __global__ __launch_bounds__(256) void attnpool_tokens_kernel(const T* __restric
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-    if ((dtype) == FFM_BF16) { CALL_BF16; } else if ((dtype) == FFM_F32) { CALL_F32; } else return FFM_EINVAL;
-
 extern "C" int ffm_stem_im2col(const float* img, void* cols, int B, int H, int W, int stride, int Kp, const float* mean3,
                                const float* std3, int dtype, void* stream) {
     if (!img || !cols || !mean3 || !std3 || B <= 0 || H <= 0 || W <= 0 || stride <= 0 || Kp < 27) return FFM_EINVAL;
@@ -659,11 +656,12 @@ extern "C" int ffm_stem_im2col(const float* img, void* cols, int B, int H, int W
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const int g = grid1d((size_t)B * Ho * Wo * Kp / (dtype == FFM_BF16 ? 8 : 4));
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((stem_im2col_kernel<bf16_t>), dim3(g), dim3(256), 0, s, img, (bf16_t*)cols, B, H, W, stride, Kp, m, sd),
-               hipLaunchKernelGGL((stem_im2col_kernel<float>), dim3(g), dim3(256), 0, s, img, (float*)cols, B, H, W, stride, Kp, m, sd))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((stem_im2col_kernel<T>), dim3(g), dim3(256), 0, s, img, (T*)cols, B, H, W, stride, Kp, m, sd);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 static bool conv_args_ok(const void* a, const void* b, int B, int H, int W, int C, int stride, int Kp, int dtype) {
@@ -678,11 +676,12 @@ extern "C" int ffm_im2col3x3(const void* x, void* cols, int B, int H, int W, int
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const int g = grid1d((size_t)B * Ho * Wo * Kp / 4);
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((im2col3x3_kernel<bf16_t>), dim3(g), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)cols, B, H, W, C, stride, Kp),
-               hipLaunchKernelGGL((im2col3x3_kernel<float>), dim3(g), dim3(256), 0, s, (const float*)x, (float*)cols, B, H, W, C, stride, Kp))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((im2col3x3_kernel<T>), dim3(g), dim3(256), 0, s, (const T*)x, (T*)cols, B, H, W, C, stride, Kp);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_col2im3x3(const void* dcols, void* dx, int B, int H, int W, int C, int stride, int Kp, int dtype,
@@ -690,11 +689,12 @@ extern "C" int ffm_col2im3x3(const void* dcols, void* dx, int B, int H, int W, i
     if (!conv_args_ok(dcols, dx, B, H, W, C, stride, Kp, dtype)) return FFM_EINVAL;
     const int g = grid1d((size_t)B * H * W * C / 4);
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((col2im3x3_kernel<bf16_t>), dim3(g), dim3(256), 0, s, (const bf16_t*)dcols, (bf16_t*)dx, B, H, W, C, stride, Kp),
-               hipLaunchKernelGGL((col2im3x3_kernel<float>), dim3(g), dim3(256), 0, s, (const float*)dcols, (float*)dx, B, H, W, C, stride, Kp))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((col2im3x3_kernel<T>), dim3(g), dim3(256), 0, s, (const T*)dcols, (T*)dx, B, H, W, C, stride, Kp);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 namespace {
@@ -721,21 +721,20 @@ extern "C" int ffm_bn_fwd(const void* x, const float* gamma, const float* beta, 
     const bn_fold fold = training ? bn_fold_geom(rows, C, vn, part_rows) : bn_fold{false, 0, 0};
     if (fold.on) {                                   // small map: no finalize launch (bn_apply_fold_kernel sums the partials)
         if (((uintptr_t)part & 15) || C % 4) return FFM_EINVAL;
-        const int gy = (C / vn + fold.strip - 1) / fold.strip;
-        int nb = part_rows;
-        if (part_rows <= 0) {
-            const int rpb = (rows + fold.G - 1) / fold.G;
-            nb = (rows + rpb - 1) / rpb;
-            DISPATCH_T(dtype,
-                       hipLaunchKernelGGL((colsum_kernel<bf16_t, 0>), dim3(nb, gy), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, part, rows, C, rpb, (bf16_t*)nullptr, fold.strip),
-                       hipLaunchKernelGGL((colsum_kernel<float, 0>), dim3(nb, gy), dim3(256), 0, s, (const float*)x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, rows, C, rpb, (float*)nullptr, fold.strip))
+        return ffm_by_storage(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            const int gy = (C / vn + fold.strip - 1) / fold.strip;
+            int nb = part_rows;
+            if (part_rows <= 0) {
+                const int rpb = (rows + fold.G - 1) / fold.G;
+                nb = (rows + rpb - 1) / rpb;
+                hipLaunchKernelGGL((colsum_kernel<T, 0>), dim3(nb, gy), dim3(256), 0, s, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, part, rows, C, rpb, (T*)nullptr, fold.strip);
+                FFM_CHECK_LAUNCH();
+            }
+            hipLaunchKernelGGL((bn_apply_fold_kernel<T>), dim3(fold.G, gy), dim3(256), 0, s, (const T*)x, part, nb, mean, rstd, run_mean, run_var, gamma, beta, (const T*)res, (T*)y, rows, C, relu, fold.strip, 0.1f, 1e-5f);
             FFM_CHECK_LAUNCH();
-        }
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((bn_apply_fold_kernel<bf16_t>), dim3(fold.G, gy), dim3(256), 0, s, (const bf16_t*)x, part, nb, mean, rstd, run_mean, run_var, gamma, beta, (const bf16_t*)res, (bf16_t*)y, rows, C, relu, fold.strip, 0.1f, 1e-5f),
-                   hipLaunchKernelGGL((bn_apply_fold_kernel<float>), dim3(fold.G, gy), dim3(256), 0, s, (const float*)x, part, nb, mean, rstd, run_mean, run_var, gamma, beta, (const float*)res, (float*)y, rows, C, relu, fold.strip, 0.1f, 1e-5f))
-        FFM_CHECK_LAUNCH();
-        return FFM_OK;
+            return FFM_OK;
+        });
     }
     if (training && part_rows > 0) {
         // the producer of x left the column sums of its row tiles behind (ffm_gemm_args.colstat_part)
@@ -745,10 +744,13 @@ extern "C" int ffm_bn_fwd(const void* x, const float* gamma, const float* beta, 
     } else if (training) {
         const int nb0 = cs_blocks(rows), rpb = (rows + nb0 - 1) / nb0, nblk = (rows + rpb - 1) / rpb;
         dim3 g(nblk, (C / (dtype == FFM_BF16 ? 8 : 4) + 255) / 256);
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((colsum_kernel<bf16_t, 0>), g, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, part, rows, C, rpb),
-                   hipLaunchKernelGGL((colsum_kernel<float, 0>), g, dim3(256), 0, s, (const float*)x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, rows, C, rpb))
-        FFM_CHECK_LAUNCH();
+        const int e = ffm_by_storage(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL((colsum_kernel<T, 0>), g, dim3(256), 0, s, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, part, rows, C, rpb);
+            FFM_CHECK_LAUNCH();
+            return FFM_OK;
+        });
+        if (e != FFM_OK) return e;
         hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + fin_sw_host(nblk) - 1) / fin_sw_host(nblk)), dim3(256), 0, s, part, nblk, rows, C, mean, rstd, run_mean,
                            run_var, 0.1f, 1e-5f);
     } else {
@@ -756,11 +758,12 @@ extern "C" int ffm_bn_fwd(const void* x, const float* gamma, const float* beta, 
     }
     FFM_CHECK_LAUNCH();
     const dim3 g2 = bn_apply_grid(rows, C, dtype == FFM_BF16 ? 8 : 4);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((bn_apply_kernel<bf16_t>), g2, dim3(256), 0, s, (const bf16_t*)x, mean, rstd, gamma, beta, (const bf16_t*)res, (bf16_t*)y, rows, C, relu),
-               hipLaunchKernelGGL((bn_apply_kernel<float>), g2, dim3(256), 0, s, (const float*)x, mean, rstd, gamma, beta, (const float*)res, (float*)y, rows, C, relu))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((bn_apply_kernel<T>), g2, dim3(256), 0, s, (const T*)x, mean, rstd, gamma, beta, (const T*)res, (T*)y, rows, C, relu);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_bn_bwd(const void* dy, const void* relu_out, const void* x, const float* gamma, const float* mean,
@@ -774,79 +777,83 @@ extern "C" int ffm_bn_bwd(const void* dy, const void* relu_out, const void* x, c
     const bn_fold fold = bn_fold_geom(rows, C, dtype == FFM_BF16 ? 8 : 4, part_rows);
     if (fold.on) {                                   // small map: column sums on strips, no finalize launch
         if (((uintptr_t)part & 15) || C % 4) return FFM_EINVAL;
-        const int gy = (C / (dtype == FFM_BF16 ? 8 : 4) + fold.strip - 1) / fold.strip;
-        const int rpb = (rows + fold.G - 1) / fold.G;
-        int nb = part_rows;                              // (> 0: the producer of dy left the column sums of its row tiles)
-        if (part_rows <= 0) {
-            nb = (rows + rpb - 1) / rpb;
-            DISPATCH_T(dtype,
-                       hipLaunchKernelGGL((colsum_kernel<bf16_t, 1>), dim3(nb, gy), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)relu_out, mean, rstd, part, rows, C, rpb, (bf16_t*)g_out, fold.strip),
-                       hipLaunchKernelGGL((colsum_kernel<float, 1>), dim3(nb, gy), dim3(256), 0, s, (const float*)dy, (const float*)x, (const float*)relu_out, mean, rstd, part, rows, C, rpb, (float*)g_out, fold.strip))
+        return ffm_by_storage(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            const int gy = (C / (dtype == FFM_BF16 ? 8 : 4) + fold.strip - 1) / fold.strip;
+            const int rpb = (rows + fold.G - 1) / fold.G;
+            int nb = part_rows;                              // (> 0: the producer of dy left the column sums of its row tiles)
+            if (part_rows <= 0) {
+                nb = (rows + rpb - 1) / rpb;
+                hipLaunchKernelGGL((colsum_kernel<T, 1>), dim3(nb, gy), dim3(256), 0, s, (const T*)dy, (const T*)x, (const T*)relu_out, mean, rstd, part, rows, C, rpb, (T*)g_out, fold.strip);
+                FFM_CHECK_LAUNCH();
+            }
+            hipLaunchKernelGGL((bn_bwd_apply_fold_kernel<T>), dim3(fold.G, gy), dim3(256), 0, s, (const T*)dy, (const T*)relu_out, (const T*)x, part, nb, mean, rstd, gamma, dgamma, dbeta, (T*)dx, rows, C, fold.strip);
             FFM_CHECK_LAUNCH();
-        }
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((bn_bwd_apply_fold_kernel<bf16_t>), dim3(fold.G, gy), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)relu_out, (const bf16_t*)x, part, nb, mean, rstd, gamma, dgamma, dbeta, (bf16_t*)dx, rows, C, fold.strip),
-                   hipLaunchKernelGGL((bn_bwd_apply_fold_kernel<float>), dim3(fold.G, gy), dim3(256), 0, s, (const float*)dy, (const float*)relu_out, (const float*)x, part, nb, mean, rstd, gamma, dgamma, dbeta, (float*)dx, rows, C, fold.strip))
-        FFM_CHECK_LAUNCH();
-        return FFM_OK;
+            return FFM_OK;
+        });
     }
     const int nb0 = cs_blocks(rows), rpb = (rows + nb0 - 1) / nb0;
     int nblk = part_rows;
     if (part_rows <= 0) {
         nblk = (rows + rpb - 1) / rpb;
         dim3 g(nblk, (C / (dtype == FFM_BF16 ? 8 : 4) + 255) / 256);
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((colsum_kernel<bf16_t, 1>), g, dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)relu_out, mean, rstd, part, rows, C, rpb, (bf16_t*)g_out),
-                   hipLaunchKernelGGL((colsum_kernel<float, 1>), g, dim3(256), 0, s, (const float*)dy, (const float*)x, (const float*)relu_out, mean, rstd, part, rows, C, rpb, (float*)g_out))
-        FFM_CHECK_LAUNCH();
+        const int e = ffm_by_storage(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL((colsum_kernel<T, 1>), g, dim3(256), 0, s, (const T*)dy, (const T*)x, (const T*)relu_out, mean, rstd, part, rows, C, rpb, (T*)g_out);
+            FFM_CHECK_LAUNCH();
+            return FFM_OK;
+        });
+        if (e != FFM_OK) return e;
     }
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + fin_sw_host(nblk) - 1) / fin_sw_host(nblk)), dim3(256), 0, s, part, nblk, rows, C, dgamma, dbeta, k12);
     FFM_CHECK_LAUNCH();
     const dim3 g2 = bn_apply_grid(rows, C, dtype == FFM_BF16 ? 8 : 4);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t>), g2, dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)relu_out, (const bf16_t*)x, mean, rstd, gamma, k12, (bf16_t*)dx, rows, C),
-               hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), g2, dim3(256), 0, s, (const float*)dy, (const float*)relu_out, (const float*)x, mean, rstd, gamma, k12, (float*)dx, rows, C))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), g2, dim3(256), 0, s, (const T*)dy, (const T*)relu_out, (const T*)x, mean, rstd, gamma, k12, (T*)dx, rows, C);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_avgpool2(const void* in, void* out, int B, int H, int W, int C, int backward, int dtype, void* stream) {
     if (!in || !out || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C % (dtype == FFM_BF16 ? 8 : 4)) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int g = grid1d((size_t)B * H * W * C / (backward ? 4 : 16));
-    if (backward) {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((avgpool2_kernel<bf16_t, true>), dim3(g), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, B, H, W, C),
-                   hipLaunchKernelGGL((avgpool2_kernel<float, true>), dim3(g), dim3(256), 0, s, (const float*)in, (float*)out, B, H, W, C))
-    } else {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((avgpool2_kernel<bf16_t, false>), dim3(g), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, B, H, W, C),
-                   hipLaunchKernelGGL((avgpool2_kernel<float, false>), dim3(g), dim3(256), 0, s, (const float*)in, (float*)out, B, H, W, C))
-    }
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (backward) {
+            hipLaunchKernelGGL((avgpool2_kernel<T, true>), dim3(g), dim3(256), 0, s, (const T*)in, (T*)out, B, H, W, C);
+        } else {
+            hipLaunchKernelGGL((avgpool2_kernel<T, false>), dim3(g), dim3(256), 0, s, (const T*)in, (T*)out, B, H, W, C);
+        }
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_add(const void* a, const void* b, void* out, int64_t n, int dtype, void* stream) {
     if (!a || !b || !out || n <= 0 || n % (dtype == FFM_BF16 ? 8 : 4)) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int g = grid1d((size_t)n / 4);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((add_kernel<bf16_t>), dim3(g), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (size_t)n),
-               hipLaunchKernelGGL((add_kernel<float>), dim3(g), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)out, (size_t)n))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((add_kernel<T>), dim3(g), dim3(256), 0, s, (const T*)a, (const T*)b, (T*)out, (size_t)n);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_relu_bwd(const void* g, const void* y, void* out, int64_t n, int dtype, void* stream) {
     if (!g || !y || !out || n <= 0 || n % (dtype == FFM_BF16 ? 8 : 4)) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int gr = grid1d((size_t)n / 4);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((relu_bwd_kernel<bf16_t>), dim3(gr), dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)y, (bf16_t*)out, (size_t)n),
-               hipLaunchKernelGGL((relu_bwd_kernel<float>), dim3(gr), dim3(256), 0, s, (const float*)g, (const float*)y, (float*)out, (size_t)n))
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((relu_bwd_kernel<T>), dim3(gr), dim3(256), 0, s, (const T*)g, (const T*)y, (T*)out, (size_t)n);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_attnpool_tokens(const void* in, const void* pos, void* out, int B, int HW, int E, int backward, int dtype,
@@ -854,15 +861,14 @@ extern "C" int ffm_attnpool_tokens(const void* in, const void* pos, void* out, i
     if (!in || !out || (!backward && !pos) || B <= 0 || HW <= 0 || E % (dtype == FFM_BF16 ? 8 : 4)) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int g = grid1d((size_t)B * (HW + 1) * E / 4);
-    if (backward) {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((attnpool_tokens_kernel<bf16_t, true>), dim3(g), dim3(256), 0, s, (const bf16_t*)in, (const bf16_t*)pos, (bf16_t*)out, B, HW, E),
-                   hipLaunchKernelGGL((attnpool_tokens_kernel<float, true>), dim3(g), dim3(256), 0, s, (const float*)in, (const float*)pos, (float*)out, B, HW, E))
-    } else {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((attnpool_tokens_kernel<bf16_t, false>), dim3(g), dim3(256), 0, s, (const bf16_t*)in, (const bf16_t*)pos, (bf16_t*)out, B, HW, E),
-                   hipLaunchKernelGGL((attnpool_tokens_kernel<float, false>), dim3(g), dim3(256), 0, s, (const float*)in, (const float*)pos, (float*)out, B, HW, E))
-    }
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (backward) {
+            hipLaunchKernelGGL((attnpool_tokens_kernel<T, true>), dim3(g), dim3(256), 0, s, (const T*)in, (const T*)pos, (T*)out, B, HW, E);
+        } else {
+            hipLaunchKernelGGL((attnpool_tokens_kernel<T, false>), dim3(g), dim3(256), 0, s, (const T*)in, (const T*)pos, (T*)out, B, HW, E);
+        }
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }

@@ -1008,53 +1008,59 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
     // BatchNorm-backward column sums exist in the kernels instantiated with the bit only (cases below; rank <= 16)
     if ((fl & FFM_EPI_BNBWD) && !(rk && (fl & ~FFM_EPI_RESIDUAL) == (FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_BNBWD)) && fl != FFM_EPI_BNBWD) return FFM_EUNSUP;
     if ((fl & FFM_EPI_BNBWD) && (fl & FFM_EPI_LORA) && a.rank > 16) return FFM_EUNSUP;
-    if ((fl & FFM_EPI_LORA) && a.rank > 16) {                             // rank-r update on the VALU: generic-flag kernels
-        if (rk) return dtype == FFM_BF16 ? launch_gemm<bf16_t, true, -1, false, true>(a, s) : launch_gemm<float, true, -1, false, true>(a, s);
-        return dtype == FFM_BF16 ? launch_gemm<bf16_t, false, -1, false, true>(a, s) : launch_gemm<float, false, -1, false, true>(a, s);
-    }
     // fewer tiles than CUs and a K loop worth pipelining (16-bit operands): the four-stage ring, one block per CU
     // (FFM_GEMM_DEEP=0: A/B runs)
     const bool deep_on = ffm_sw().gemm_deep;
     const long tiles_ = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     const bool deep = deep_on && dtype == FFM_BF16 && tiles_ <= 256 && (size_t)a.K * es / KT_BYTES >= 6;
-#define FFM_GEMM_CASE(RKB, F)                                                                   \
-    case F:                                                                                      \
-        if (deep) {                          /* (its LDS need exceeds 160 KB for this rank / epilogue: two-buffer loop) */ \
-            const int e4 = launch_gemm<bf16_t, RKB, F, false, false, 4>(a, s);                   \
-            if (e4 != FFM_EUNSUP) return e4;                                                     \
-        }                                                                                        \
-        return dtype == FFM_BF16 ? launch_gemm<bf16_t, RKB, F>(a, s) : launch_gemm<float, RKB, F>(a, s);
-    if (rk) {
-        switch (fl) {
-            FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)                        // c_fc forward
-            FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)    // ... of the evaluation pass
-            FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)                    // c_proj forward
-            FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU)                    // dX of c_proj
-            FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR)                                    // dX of c_fc
-            FFM_GEMM_CASE(true, FFM_EPI_LORA)                                                      // RN50 conv1 / conv3 (no bias)
-            FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA)                                       // RN50 attention-pool projections
-            FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_RESIDUAL)                 // RN50 dX of conv1 + identity path
-            FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_BNBWD)                    // RN50 dX of conv3 + bn2's backward sums
-            FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_RESIDUAL | FFM_EPI_BNBWD) // dX of conv1 + identity + the NEXT block's bn3 sums
-            default: return dtype == FFM_BF16 ? launch_gemm<bf16_t, true, -1>(a, s) : launch_gemm<float, true, -1>(a, s);
+    // (the ring exists in 16-bit storage only; where its LDS need exceeds 160 KB for this rank / epilogue: two-buffer loop)
+#define FFM_GEMM_CASE(RKB, F)                                                  \
+    case F:                                                                     \
+        if constexpr (sizeof(T) == 2) {                                         \
+            if (deep) {                                                         \
+                const int e4 = launch_gemm<T, RKB, F, false, false, 4>(a, s);   \
+                if (e4 != FFM_EUNSUP) return e4;                                \
+            }                                                                   \
+        }                                                                       \
+        return launch_gemm<T, RKB, F>(a, s);
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if ((fl & FFM_EPI_LORA) && a.rank > 16) {                         // rank-r update on the VALU: generic-flag kernels
+            if (rk) return launch_gemm<T, true, -1, false, true>(a, s);
+            return launch_gemm<T, false, -1, false, true>(a, s);
         }
-    }
-    switch (fl) {
-        FFM_GEMM_CASE(false, 0)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_RESIDUAL)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_GELU)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)
-        FFM_GEMM_CASE(false, FFM_EPI_DGELU)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)
-        FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)
-        FFM_GEMM_CASE(false, FFM_EPI_LORA | FFM_EPI_LORA_KR)
-        FFM_GEMM_CASE(false, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU)
-        FFM_GEMM_CASE(false, FFM_EPI_BNBWD)                                                      // a plain dX product + the sums
-        default: return dtype == FFM_BF16 ? launch_gemm<bf16_t, false, -1>(a, s) : launch_gemm<float, false, -1>(a, s);
-    }
+        if (rk) {
+            switch (fl) {
+                FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)                        // c_fc forward
+                FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)    // ... of the evaluation pass
+                FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)                    // c_proj forward
+                FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU)                    // dX of c_proj
+                FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR)                                    // dX of c_fc
+                FFM_GEMM_CASE(true, FFM_EPI_LORA)                                                      // RN50 conv1 / conv3 (no bias)
+                FFM_GEMM_CASE(true, FFM_EPI_BIAS | FFM_EPI_LORA)                                       // RN50 attention-pool projections
+                FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_RESIDUAL)                 // RN50 dX of conv1 + identity path
+                FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_BNBWD)                    // RN50 dX of conv3 + bn2's backward sums
+                FFM_GEMM_CASE(true, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_RESIDUAL | FFM_EPI_BNBWD) // dX of conv1 + identity + the NEXT block's bn3 sums
+                default: return launch_gemm<T, true, -1>(a, s);
+            }
+        }
+        switch (fl) {
+            FFM_GEMM_CASE(false, 0)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_RESIDUAL)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_GELU)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)
+            FFM_GEMM_CASE(false, FFM_EPI_DGELU)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_GELU | FFM_EPI_GELU_ONLY)
+            FFM_GEMM_CASE(false, FFM_EPI_BIAS | FFM_EPI_LORA | FFM_EPI_RESIDUAL)
+            FFM_GEMM_CASE(false, FFM_EPI_LORA | FFM_EPI_LORA_KR)
+            FFM_GEMM_CASE(false, FFM_EPI_LORA | FFM_EPI_LORA_KR | FFM_EPI_DGELU)
+            FFM_GEMM_CASE(false, FFM_EPI_BNBWD)                                                      // a plain dX product + the sums
+            default: return launch_gemm<T, false, -1>(a, s);
+        }
+    });
 #undef FFM_GEMM_CASE
 }
 
@@ -1423,40 +1429,45 @@ static int conv3x3_impl(const void* x, const void* w, void* y, int B, int H, int
     // column tiles when the launch has fewer than t 128x128 tiles (measured at t = 512 / 1000 on RN50 bs 32: no gain)
     const int t128 = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     const int narrow_max = ffm_sw().conv_narrow_max;
-    if (S == 1 && narrow_max >= 0 && (a.N == 32 || a.N == 64 || (a.N % 64 == 0 && t128 < narrow_max))) {
-        if (bnb) {
-            if (a.N == 32) return dtype == FFM_BF16 ? launch_conv_narrow<bf16_t, 32, true>(ka, s) : launch_conv_narrow<float, 32, true>(ka, s);
-            return dtype == FFM_BF16 ? launch_conv_narrow<bf16_t, 64, true>(ka, s) : launch_conv_narrow<float, 64, true>(ka, s);
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        constexpr bool ring = sizeof(T) == 2;                      // (the four-stage ring: 16-bit storage only)
+        if (S == 1 && narrow_max >= 0 && (a.N == 32 || a.N == 64 || (a.N % 64 == 0 && t128 < narrow_max))) {
+            if (bnb) return a.N == 32 ? launch_conv_narrow<T, 32, true>(ka, s) : launch_conv_narrow<T, 64, true>(ka, s);
+            return a.N == 32 ? launch_conv_narrow<T, 32>(ka, s) : launch_conv_narrow<T, 64>(ka, s);
         }
-        if (a.N == 32) return dtype == FFM_BF16 ? launch_conv_narrow<bf16_t, 32>(ka, s) : launch_conv_narrow<float, 32>(ka, s);
-        return dtype == FFM_BF16 ? launch_conv_narrow<bf16_t, 64>(ka, s) : launch_conv_narrow<float, 64>(ka, s);
-    }
-    if (bnb && S == 1) {
-        if (deep && dtype == FFM_BF16) return launch_gemm<bf16_t, false, FFM_EPI_BNBWD, true, false, 4>(a, s, &ka);
-        return dtype == FFM_BF16 ? launch_gemm<bf16_t, false, FFM_EPI_BNBWD, true>(a, s, &ka) : launch_gemm<float, false, FFM_EPI_BNBWD, true>(a, s, &ka);
-    }
-    const int e = (deep && dtype == FFM_BF16) ? launch_gemm<bf16_t, false, 0, true, false, 4>(a, s, &ka)
-                  : dtype == FFM_BF16 ? launch_gemm<bf16_t, false, 0, true>(a, s, &ka) : launch_gemm<float, false, 0, true>(a, s, &ka);
-    if (e || ka.ksplit <= 1) return e;
-    const size_t total = (size_t)a.M * a.N, total4 = total / 4;
-    if (colstat_part && splitk_cs_ok(a.M, a.N)) {
-        const int R = splitk_cs_rows(a.M), nb = (a.M + R - 1) / R;
-#define FFM_SKCS(T, B_) hipLaunchKernelGGL((splitk_reduce_cs_kernel<T, B_>), dim3(nb, (a.N + 63) / 64), dim3(256), 0, s, ka.part, (T*)y, a.M, a.N, total, \
-                                           ka.ksplit, R, colstat_part, (const T*)bn_x, (const T*)bn_mask, bn_mean, bn_rstd)
-        if (dtype == FFM_BF16) { if (bnb) FFM_SKCS(bf16_t, true); else FFM_SKCS(bf16_t, false); }
-        else { if (bnb) FFM_SKCS(float, true); else FFM_SKCS(float, false); }
-#undef FFM_SKCS
+        if (bnb && S == 1) {
+            if constexpr (ring) {
+                if (deep) return launch_gemm<T, false, FFM_EPI_BNBWD, true, false, 4>(a, s, &ka);
+            }
+            return launch_gemm<T, false, FFM_EPI_BNBWD, true>(a, s, &ka);
+        }
+        const int e = [&] {
+            if constexpr (ring) {
+                if (deep) return launch_gemm<T, false, 0, true, false, 4>(a, s, &ka);
+            }
+            return launch_gemm<T, false, 0, true>(a, s, &ka);
+        }();
+        if (e || ka.ksplit <= 1) return e;
+        const size_t total = (size_t)a.M * a.N, total4 = total / 4;
+        if (colstat_part && splitk_cs_ok(a.M, a.N)) {
+            const int R = splitk_cs_rows(a.M), nb = (a.M + R - 1) / R;
+            const dim3 g(nb, (a.N + 63) / 64);
+            if (bnb)
+                hipLaunchKernelGGL((splitk_reduce_cs_kernel<T, true>), g, dim3(256), 0, s, ka.part, (T*)y, a.M, a.N, total, ka.ksplit, R,
+                                   colstat_part, (const T*)bn_x, (const T*)bn_mask, bn_mean, bn_rstd);
+            else
+                hipLaunchKernelGGL((splitk_reduce_cs_kernel<T, false>), g, dim3(256), 0, s, ka.part, (T*)y, a.M, a.N, total, ka.ksplit, R,
+                                   colstat_part, (const T*)bn_x, (const T*)bn_mask, bn_mean, bn_rstd);
+            FFM_CHECK_LAUNCH();
+            return FFM_OK;
+        }
+        size_t blocks = (total4 + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, s, ka.part, (T*)y, total4, total, ka.ksplit);
         FFM_CHECK_LAUNCH();
         return FFM_OK;
-    }
-    size_t blocks = (total4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, ka.part, (bf16_t*)y, total4, total, ka.ksplit);
-    else
-        hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, ka.part, (float*)y, total4, total, ka.ksplit);
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    });
 }
 
 // The host queries: which kernel ffm_gemm_nt would launch for this product, and its tile (128x128, 8 waves per CU: this file's)
@@ -1500,24 +1511,18 @@ extern "C" int ffm_gemm_tile_shape(int M, int N, int K, int flags, int rank, int
 extern "C" int ffm_lora_pack_multi(const ffm_pack_desc* descs_dev, int ndesc, int max_K, int dtype, void* stream) {
     if (!descs_dev || ndesc <= 0 || max_K <= 0) return FFM_EINVAL;
     dim3 grid((RK_ROWS * max_K + 255) / 256, ndesc);
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((lora_pack_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, descs_dev);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((lora_pack_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, descs_dev);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((lora_pack_kernel<typename decltype(tag)::type>), grid, dim3(256), 0, (hipStream_t)stream, descs_dev);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_lora_pack_ln(const ffm_pack_desc* descs_dev, int ndesc, int dtype, void* stream) {
     if (!descs_dev || ndesc <= 0) return FFM_EINVAL;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((lora_pack_ln_kernel<bf16_t>), dim3(ndesc), dim3(256), 0, (hipStream_t)stream, descs_dev);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((lora_pack_ln_kernel<float>), dim3(ndesc), dim3(256), 0, (hipStream_t)stream, descs_dev);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((lora_pack_ln_kernel<typename decltype(tag)::type>), dim3(ndesc), dim3(256), 0, (hipStream_t)stream, descs_dev);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }

@@ -36,7 +36,7 @@ template <> struct SkOps<bf16_t, bf16_t, false> {
     static __device__ __forceinline__ void mma(f32x4& acc, const afrag& a, const bprep& b) { Mma16<bf16_t>::mma(acc, a.v, b); }
 };
 template <> struct SkOps<float, float, false> {
-    static constexpr int KS = 16, UN = 8;
+    [[maybe_unused]] static constexpr int KS = 16, UN = 8;      // (unused in the half twin, which names no float kernel)
     struct afrag { f32x4 v; };
     typedef f32x4 braw;
     typedef f32x4 bprep;
@@ -79,7 +79,7 @@ template <> struct SkOps<float, float, true> {
 typedef _Float16 sk_half8 __attribute__((ext_vector_type(8)));
 template <> struct SkOps<float, _Float16, true> {
     typedef SkOps<float, float, true> F;
-    static constexpr int KS = F::KS, UN = F::UN;
+    [[maybe_unused]] static constexpr int KS = F::KS, UN = F::UN;
     typedef F::afrag afrag;
     typedef sk_half8 braw;
     typedef F::bprep bprep;
@@ -546,12 +546,17 @@ extern "C" int64_t ffm_gemm_splitk_floats(int M, int N, int K, int dtype) {
 #endif
 
 int ffm_skinny_launch(const ffm_gemm_args& a, int dtype, hipStream_t s) {
-    if (a.sk_part && (dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) && sk_slices(a.M, a.N, a.K) > 0 && !(a.ldc & 3)) {
-        const int e = dtype == FFM_F32_X3 ? launch_splitk<float>(a, s) : launch_splitk<_Float16>(a, s);
-        if (e != FFM_EUNSUP) return e;
-    }
-    if (dtype == FFM_F32) return launch_waves<float, float, false>(a, s);
-    if (dtype == FFM_F32_X3) return launch_waves<float, float, true>(a, s);
-    if (dtype == FFM_F32_X3_W16) return launch_waves<float, _Float16, true>(a, s);
-    return launch_waves<bf16_t, bf16_t, false>(a, s);
+    if (dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16)
+        return ffm_by_split_weight(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type TB;
+            if (a.sk_part && sk_slices(a.M, a.N, a.K) > 0 && !(a.ldc & 3)) {
+                const int e = launch_splitk<TB>(a, s);
+                if (e != FFM_EUNSUP) return e;
+            }
+            return launch_waves<float, TB, true>(a, s);
+        });
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        return launch_waves<T, T, false>(a, s);
+    });
 }

@@ -345,16 +345,13 @@ extern "C" int ffm_head_fwd(const void* f, const float* tbar, const float* logit
     if (!f || !tbar || !logit_scale || !fbar || !rnorm || !logits_img) return FFM_EINVAL;
     if (B <= 0 || L <= 1 || D <= 0 || (D & 3) || D > 4 * 64 * HD_MAXV || n_cls <= 0 || n_cls > HD_MAXC) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((head_fwd_kernel<bf16_t>), dim3(B), dim3(64 * HD_NW), 0, s, (const bf16_t*)f, tbar, logit_scale,
-                           fbar, rnorm, logits_img, L, D, n_cls);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((head_fwd_kernel<float>), dim3(B), dim3(64 * HD_NW), 0, s, (const float*)f, tbar, logit_scale,
-                           fbar, rnorm, logits_img, L, D, n_cls);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((head_fwd_kernel<T>), dim3(B), dim3(64 * HD_NW), 0, s, (const T*)f, tbar, logit_scale, fbar, rnorm,
+                           logits_img, L, D, n_cls);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_ce_loss(const float* logits_img, const int64_t* label, float* logits, float* prob, float* loss,
@@ -385,15 +382,14 @@ extern "C" int ffm_head_bwd(const void* f, const float* tbar, const float* logit
     if (!f || !tbar || !logit_scale || !fbar || !rnorm || !dlogits_img || !df || !dtbar) return FFM_EINVAL;
     if (B <= 0 || L <= 1 || D <= 0 || (D & 3) || D > 4 * 64 * HD_MAXV || n_cls <= 0 || n_cls > HD_MAXC) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((head_bwd_kernel<bf16_t>), dim3(B, 4), dim3(64 * HD_NW), 0, s, (const bf16_t*)f, tbar, logit_scale,
-                           rnorm, dlogits_img, (bf16_t*)df, L, D, n_cls);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((head_bwd_kernel<float>), dim3(B, 4), dim3(64 * HD_NW), 0, s, (const float*)f, tbar, logit_scale,
-                           rnorm, dlogits_img, (float*)df, L, D, n_cls);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
+    const int e = ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((head_bwd_kernel<T>), dim3(B, 4), dim3(64 * HD_NW), 0, s, (const T*)f, tbar, logit_scale, rnorm,
+                           dlogits_img, (T*)df, L, D, n_cls);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
+    if (e != FFM_OK) return e;
     hipLaunchKernelGGL(head_dtbar_kernel, dim3((n_cls * D + 255) / 256), dim3(256), 0, s, fbar, logit_scale,
                        dlogits_img, dtbar, B, D, n_cls);
     FFM_CHECK_LAUNCH();

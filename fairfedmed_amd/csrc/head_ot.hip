@@ -274,13 +274,13 @@ extern "C" int ffm_ot_head_fwd(const void* f, const float* tn, const float* logi
     const int rows = B * L;
     // (:724-726) top_percent = min(torch.sum(xx).item(), TOP_PERCENT); xx sums to 1 per problem, so sum(xx) = #problems
     top_percent = top_percent < (float)nprob ? top_percent : (float)nprob;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((ot_sim_kernel<bf16_t>), dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16_t*)f, tn, rnorm, sim, B, L, D, n_cls, N);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((ot_sim_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)f, tn, rnorm, sim, B, L, D, n_cls, N);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
+    const int e = ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((ot_sim_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T*)f, tn, rnorm, sim, B, L, D, n_cls, N);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
+    if (e != FFM_OK) return e;
     if (mode == 1) {
         hipLaunchKernelGGL((ot_plan_kernel<1, 1>), dim3(nprob), dim3(threads), 0, s, sim, errs, istop, T, tsum, M, N, nprob, eps, top_percent, max_iter);
         FFM_CHECK_LAUNCH();
@@ -307,17 +307,12 @@ extern "C" int ffm_ot_head_bwd(const void* f, const float* tn, const float* logi
     if (!args_ok(B, L, D, n_cls, N, 1)) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int rows = B * L;
-    if (dtype == FFM_BF16) {
-        hipLaunchKernelGGL((ot_bwd_feat_kernel<bf16_t>), dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16_t*)f, tn, logit_scale, rnorm, T, dlogits_img, (bf16_t*)df, B, L, D, n_cls, N);
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type E;                 // (T is the transport plan here)
+        hipLaunchKernelGGL((ot_bwd_feat_kernel<E>), dim3((rows + 3) / 4), dim3(256), 0, s, (const E*)f, tn, logit_scale, rnorm, T, dlogits_img, (E*)df, B, L, D, n_cls, N);
         FFM_CHECK_LAUNCH();
-        hipLaunchKernelGGL((ot_bwd_text_kernel<bf16_t>), dim3(B, n_cls * N), dim3(256), 0, s, (const bf16_t*)f, logit_scale, rnorm, T, dlogits_img, dtn_part, L, D, n_cls, N);
-    } else if (dtype == FFM_F32) {
-        hipLaunchKernelGGL((ot_bwd_feat_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)f, tn, logit_scale, rnorm, T, dlogits_img, (float*)df, B, L, D, n_cls, N);
+        hipLaunchKernelGGL((ot_bwd_text_kernel<E>), dim3(B, n_cls * N), dim3(256), 0, s, (const E*)f, logit_scale, rnorm, T, dlogits_img, dtn_part, L, D, n_cls, N);
         FFM_CHECK_LAUNCH();
-        hipLaunchKernelGGL((ot_bwd_text_kernel<float>), dim3(B, n_cls * N), dim3(256), 0, s, (const float*)f, logit_scale, rnorm, T, dlogits_img, dtn_part, L, D, n_cls, N);
-    } else {
-        return FFM_EINVAL;
-    }
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+        return FFM_OK;
+    });
 }

@@ -738,15 +738,20 @@ extern "C" int ffm_lora_down(const void* x, int ldx, const float* P, int layout_
         FFM_CHECK_LAUNCH();
         return FFM_OK;
     }
-#define DOWN(T, RP, RR, J0) launch_down<T, RP>(x, ldx, P, layout_rk, S, attr, M, K, RR, G, rows_per_sample, scaling, \
-                                               lambda_group, t, ts, t_fwd, ds_part, r, J0, s)
-    if (r > 16) {                       // rank 17..32: two passes over the rank (second pass re-reads x)
-        int e = dtype == FFM_BF16 ? DOWN(bf16_t, 16, 16, 0) : DOWN(float, 16, 16, 0);
-        if (e) return e;
-        return dtype == FFM_BF16 ? DOWN(bf16_t, 16, r - 16, 16) : DOWN(float, 16, r - 16, 16);
-    }
-    if (dtype == FFM_BF16) return r <= 8 ? DOWN(bf16_t, 8, r, 0) : DOWN(bf16_t, 16, r, 0);
-    return r <= 4 ? DOWN(float, 4, r, 0) : r <= 8 ? DOWN(float, 8, r, 0) : DOWN(float, 16, r, 0);
+#define DOWN(RP, RR, J0) launch_down<T, RP>(x, ldx, P, layout_rk, S, attr, M, K, RR, G, rows_per_sample, scaling, \
+                                            lambda_group, t, ts, t_fwd, ds_part, r, J0, s)
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (r > 16) {                   // rank 17..32: two passes over the rank (second pass re-reads x)
+            int e = DOWN(16, 16, 0);
+            if (e) return e;
+            return DOWN(16, r - 16, 16);
+        }
+        if constexpr (sizeof(T) == 4) {                    // (down_rp: four rank slots per lane group in float32 only)
+            if (r <= 4) return DOWN(4, r, 0);
+        }
+        return r <= 8 ? DOWN(8, r, 0) : DOWN(16, r, 0);
+    });
 #undef DOWN
 }
 
@@ -764,14 +769,16 @@ extern "C" int ffm_lora_grad_partial(const void* x, int ldx, const float* v, int
         }
         return FFM_OK;
     }
-#define GRAD(T, RP, RR, J0) launch_grad<T, RP>(x, ldx, v, M, K, RR, part, r, J0, s)
-    if (r > 16) {
-        int e = dtype == FFM_BF16 ? GRAD(bf16_t, 16, 16, 0) : GRAD(float, 16, 16, 0);
-        if (e) return e;
-        return dtype == FFM_BF16 ? GRAD(bf16_t, 16, r - 16, 16) : GRAD(float, 16, r - 16, 16);
-    }
-    if (dtype == FFM_BF16) return r <= 4 ? GRAD(bf16_t, 4, r, 0) : r <= 8 ? GRAD(bf16_t, 8, r, 0) : GRAD(bf16_t, 16, r, 0);
-    return r <= 4 ? GRAD(float, 4, r, 0) : r <= 8 ? GRAD(float, 8, r, 0) : GRAD(float, 16, r, 0);
+#define GRAD(RP, RR, J0) launch_grad<T, RP>(x, ldx, v, M, K, RR, part, r, J0, s)
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (r > 16) {
+            int e = GRAD(16, 16, 0);
+            if (e) return e;
+            return GRAD(16, r - 16, 16);
+        }
+        return r <= 4 ? GRAD(4, r, 0) : r <= 8 ? GRAD(8, r, 0) : GRAD(16, r, 0);
+    });
 #undef GRAD
 }
 

@@ -1,5 +1,5 @@
 // Flat-buffer parameter kernels: fused SGD-momentum over all trainable tensors,
-// the FedAvg round-boundary helpers, and load-time dtype casts / transposes.
+// and the FedAvg round-boundary helpers.  All float32: no `dtype` argument, no half twin.
 #include "common.h"
 
 namespace {
@@ -105,38 +105,6 @@ __global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ avg,
 #pragma clang fp contract(off)      // three roundings, as `(1 - b) * avg + b * w_g` has in the reference (utils/fed_utils.py:98)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = (1.0f - beta) * avg[i] + beta * prev[i];
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst,
-                                                            int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = Elem<T>::from_f(src[i]);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void cast_to_f32_kernel(const T* __restrict__ src, float* __restrict__ dst,
-                                                          int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = Elem<T>::to_f(src[i]);
-}
-
-// dst[c][r] = src[r][c], 32x32 tiles through LDS
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_cast_kernel(const float* __restrict__ src, T* __restrict__ dst,
-                                                             int rows, int cols) {
-    __shared__ float tile[32][33];
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int i = ty; i < 32; i += 8) {
-        const int r = r0 + i, c = c0 + tx;
-        tile[i][tx] = (r < rows && c < cols) ? src[(size_t)r * cols + c] : 0.f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int c = c0 + i, r = r0 + tx;
-        if (c < cols && r < rows) dst[(size_t)c * rows + r] = Elem<T>::from_f(tile[tx][i]);
-    }
 }
 
 inline int grid_for(int64_t n) {
@@ -524,46 +492,6 @@ extern "C" int ffm_fedavg_finish(float* avg, const float* prev, float* out, int6
         FFM_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n)), dim3(256), 0, s, avg, prev, out, n, beta);
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
-}
-
-extern "C" int ffm_cast_f32_to(const float* src, void* dst, int64_t n, int dtype, void* stream) {
-    if (!src || !dst || n <= 0) return FFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((cast_from_f32_kernel<bf16_t>), dim3(grid_for(n)), dim3(256), 0, s, src, (bf16_t*)dst, n);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((cast_from_f32_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, src, (float*)dst, n);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
-}
-
-extern "C" int ffm_cast_to_f32(const void* src, float* dst, int64_t n, int dtype, void* stream) {
-    if (!src || !dst || n <= 0) return FFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((cast_to_f32_kernel<bf16_t>), dim3(grid_for(n)), dim3(256), 0, s, (const bf16_t*)src, dst, n);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((cast_to_f32_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)src, dst, n);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
-}
-
-extern "C" int ffm_transpose_cast(const float* src, void* dst, int rows, int cols, int dtype, void* stream) {
-    if (!src || !dst || rows <= 0 || cols <= 0) return FFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((transpose_cast_kernel<bf16_t>), grid, dim3(256), 0, s, src, (bf16_t*)dst, rows, cols);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((transpose_cast_kernel<float>), grid, dim3(256), 0, s, src, (float*)dst, rows, cols);
-    else
-        return FFM_EINVAL;
     FFM_CHECK_LAUNCH();
     return FFM_OK;
 }

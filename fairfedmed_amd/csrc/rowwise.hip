@@ -221,6 +221,44 @@ __global__ __launch_bounds__(256) void embed_lnpre_kernel(const T* __restrict__ 
 
 inline bool bad_width(int width) { return width <= 0 || (width & 7) || width > 8 * 64 * MAXC; }
 
+// load-time dtype casts / transposes
+template <typename T>
+__global__ __launch_bounds__(256) void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst,
+                                                            int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = Elem<T>::from_f(src[i]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cast_to_f32_kernel(const T* __restrict__ src, float* __restrict__ dst,
+                                                          int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = Elem<T>::to_f(src[i]);
+}
+
+// dst[c][r] = src[r][c], 32x32 tiles through LDS
+template <typename T>
+__global__ __launch_bounds__(256) void transpose_cast_kernel(const float* __restrict__ src, T* __restrict__ dst,
+                                                             int rows, int cols) {
+    __shared__ float tile[32][33];
+    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+    for (int i = ty; i < 32; i += 8) {
+        const int r = r0 + i, c = c0 + tx;
+        tile[i][tx] = (r < rows && c < cols) ? src[(size_t)r * cols + c] : 0.f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int c = c0 + i, r = r0 + tx;
+        if (c < cols && r < rows) dst[(size_t)c * rows + r] = Elem<T>::from_f(tile[tx][i]);
+    }
+}
+
+inline int cast_grid(int64_t n) {
+    int64_t b = (n + 255) / 256;
+    return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
+}
+
 }  // namespace
 
 extern "C" int ffm_layernorm_fwd(const void* x, void* y, const float* gamma, const float* beta, float* mean,
@@ -229,17 +267,13 @@ extern "C" int ffm_layernorm_fwd(const void* x, void* y, const float* gamma, con
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((rows + 3) / 4), block(256);
     const bool narrow = width <= 8 * 64 * 2;
-#define LN_FWD(T, MC) hipLaunchKernelGGL((layernorm_fwd_kernel<T, MC>), grid, block, 0, s, (const T*)x, (T*)y, gamma, beta, mean, rstd, rows, width)
-    if (dtype == FFM_BF16) {
-        if (narrow) LN_FWD(bf16_t, 2); else LN_FWD(bf16_t, 4);
-    } else if (dtype == FFM_F32) {
-        if (narrow) LN_FWD(float, 2); else LN_FWD(float, 4);
-    } else {
-        return FFM_EINVAL;
-    }
-#undef LN_FWD
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (narrow) hipLaunchKernelGGL((layernorm_fwd_kernel<T, 2>), grid, block, 0, s, (const T*)x, (T*)y, gamma, beta, mean, rstd, rows, width);
+        else hipLaunchKernelGGL((layernorm_fwd_kernel<T, 4>), grid, block, 0, s, (const T*)x, (T*)y, gamma, beta, mean, rstd, rows, width);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
@@ -249,17 +283,13 @@ extern "C" int ffm_layernorm_bwd(const void* dy, const void* x, const float* gam
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((rows + 3) / 4), block(256);
     const bool narrow = width <= 8 * 64 * 2;
-#define LN_BWD(T, MC) hipLaunchKernelGGL((layernorm_bwd_kernel<T, MC>), grid, block, 0, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)res, (T*)out, rows, width)
-    if (dtype == FFM_BF16) {
-        if (narrow) LN_BWD(bf16_t, 2); else LN_BWD(bf16_t, 4);
-    } else if (dtype == FFM_F32) {
-        if (narrow) LN_BWD(float, 2); else LN_BWD(float, 4);
-    } else {
-        return FFM_EINVAL;
-    }
-#undef LN_BWD
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (narrow) hipLaunchKernelGGL((layernorm_bwd_kernel<T, 2>), grid, block, 0, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)res, (T*)out, rows, width);
+        else hipLaunchKernelGGL((layernorm_bwd_kernel<T, 4>), grid, block, 0, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)res, (T*)out, rows, width);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_patchify(const float* img, void* cols, int B, int H, int W, int patch, const float* mean3,
@@ -273,16 +303,12 @@ extern "C" int ffm_patchify(const float* img, void* cols, int B, int H, int W, i
     const size_t total = (size_t)B * (H / patch) * (W / patch) * 3 * patch * (patch / 4);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((patchify_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, img, (bf16_t*)cols, B, H, W,
-                           patch, m, sd, prenormalised);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((patchify_kernel<float>), dim3(blocks), dim3(256), 0, s, img, (float*)cols, B, H, W, patch,
-                           m, sd, prenormalised);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((patchify_kernel<T>), dim3(blocks), dim3(256), 0, s, img, (T*)cols, B, H, W, patch, m, sd, prenormalised);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_embed_lnpre(const void* patch, const void* cls, const void* pos, const float* gamma,
@@ -290,14 +316,45 @@ extern "C" int ffm_embed_lnpre(const void* patch, const void* cls, const void* p
     if (!patch || !cls || !pos || !gamma || !beta || !x || B <= 0 || L <= 1 || bad_width(width)) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((B * L + 3) / 4), block(256);
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((embed_lnpre_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)patch, (const bf16_t*)cls,
-                           (const bf16_t*)pos, gamma, beta, (bf16_t*)x, rowstat, B, L, width);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((embed_lnpre_kernel<float>), grid, block, 0, s, (const float*)patch, (const float*)cls,
-                           (const float*)pos, gamma, beta, (float*)x, rowstat, B, L, width);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((embed_lnpre_kernel<T>), grid, block, 0, s, (const T*)patch, (const T*)cls, (const T*)pos, gamma, beta,
+                           (T*)x, rowstat, B, L, width);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
+}
+
+extern "C" int ffm_cast_f32_to(const float* src, void* dst, int64_t n, int dtype, void* stream) {
+    if (!src || !dst || n <= 0) return FFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((cast_from_f32_kernel<T>), dim3(cast_grid(n)), dim3(256), 0, s, src, (T*)dst, n);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
+}
+
+extern "C" int ffm_cast_to_f32(const void* src, float* dst, int64_t n, int dtype, void* stream) {
+    if (!src || !dst || n <= 0) return FFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((cast_to_f32_kernel<T>), dim3(cast_grid(n)), dim3(256), 0, s, (const T*)src, dst, n);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
+}
+
+extern "C" int ffm_transpose_cast(const float* src, void* dst, int rows, int cols, int dtype, void* stream) {
+    if (!src || !dst || rows <= 0 || cols <= 0) return FFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((cols + 31) / 32, (rows + 31) / 32);
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((transpose_cast_kernel<T>), grid, dim3(256), 0, s, src, (T*)dst, rows, cols);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }

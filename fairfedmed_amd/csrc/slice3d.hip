@@ -630,16 +630,12 @@ extern "C" int ffm_patchify_minmax(const float* conv, const float* mnmx, int32_t
     int blocks = (int)((total + 255) / 256);
     if (blocks > 8192) blocks = 8192;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((patchify_minmax_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, conv, mnmx, cnt, (bf16_t*)cols,
-                           N, H, W, patch, m, sd);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((patchify_minmax_kernel<float>), dim3(blocks), dim3(256), 0, s, conv, mnmx, cnt, (float*)cols, N,
-                           H, W, patch, m, sd);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((patchify_minmax_kernel<T>), dim3(blocks), dim3(256), 0, s, conv, mnmx, cnt, (T*)cols, N, H, W, patch, m, sd);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 extern "C" int ffm_embed_lnpre_bwd(const void* dx, const void* patch, const void* pos, const float* gamma, void* dpatch,
@@ -648,23 +644,25 @@ extern "C" int ffm_embed_lnpre_bwd(const void* dx, const void* patch, const void
         return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((B * L + 3) / 4), block(256);
-    if (dtype == FFM_BF16 && width % 8 == 0 && width <= 1024) {
-        if (width <= 512)
-            hipLaunchKernelGGL((embed_lnpre_bwd2_kernel<bf16_t, 1>), grid, block, 0, s, (const bf16_t*)dx, (const bf16_t*)patch,
-                               (const bf16_t*)pos, gamma, (bf16_t*)dpatch, B, L, width);
-        else
-            hipLaunchKernelGGL((embed_lnpre_bwd2_kernel<bf16_t, 2>), grid, block, 0, s, (const bf16_t*)dx, (const bf16_t*)patch,
-                               (const bf16_t*)pos, gamma, (bf16_t*)dpatch, B, L, width);
-    } else if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((embed_lnpre_bwd_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dx, (const bf16_t*)patch,
-                           (const bf16_t*)pos, gamma, (bf16_t*)dpatch, B, L, width);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((embed_lnpre_bwd_kernel<float>), grid, block, 0, s, (const float*)dx, (const float*)patch,
-                           (const float*)pos, gamma, (float*)dpatch, B, L, width);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
-    return FFM_OK;
+    return ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if constexpr (sizeof(T) == 2) {                        // (the 8-per-chunk kernel exists for the 16-bit type only)
+            if (width % 8 == 0 && width <= 1024) {
+                if (width <= 512)
+                    hipLaunchKernelGGL((embed_lnpre_bwd2_kernel<T, 1>), grid, block, 0, s, (const T*)dx, (const T*)patch,
+                                       (const T*)pos, gamma, (T*)dpatch, B, L, width);
+                else
+                    hipLaunchKernelGGL((embed_lnpre_bwd2_kernel<T, 2>), grid, block, 0, s, (const T*)dx, (const T*)patch,
+                                       (const T*)pos, gamma, (T*)dpatch, B, L, width);
+                FFM_CHECK_LAUNCH();
+                return FFM_OK;
+            }
+        }
+        hipLaunchKernelGGL((embed_lnpre_bwd_kernel<T>), grid, block, 0, s, (const T*)dx, (const T*)patch, (const T*)pos, gamma,
+                           (T*)dpatch, B, L, width);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
 }
 
 #define SLICE_BWD_BLOCKS 64   /* partial sums per ViT image in the un-patchify pass */
@@ -677,15 +675,13 @@ extern "C" int ffm_slice_bwd(const void* dcols, const float* img, const float* c
     const f32x4 sd = {std3[0], std3[1], std3[2], 1.f};
     hipStream_t s = (hipStream_t)stream;
     dim3 g1(SLICE_BWD_BLOCKS, N);
-    if (dtype == FFM_BF16)
-        hipLaunchKernelGGL((unpatchify_bwd_kernel<bf16_t>), g1, dim3(256), 0, s, (const bf16_t*)dcols, conv, mnmx, dconv,
-                           ab_part, N, H, W, patch, sd);
-    else if (dtype == FFM_F32)
-        hipLaunchKernelGGL((unpatchify_bwd_kernel<float>), g1, dim3(256), 0, s, (const float*)dcols, conv, mnmx, dconv,
-                           ab_part, N, H, W, patch, sd);
-    else
-        return FFM_EINVAL;
-    FFM_CHECK_LAUNCH();
+    const int e = ffm_by_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL((unpatchify_bwd_kernel<T>), g1, dim3(256), 0, s, (const T*)dcols, conv, mnmx, dconv, ab_part, N, H, W, patch, sd);
+        FFM_CHECK_LAUNCH();
+        return FFM_OK;
+    });
+    if (e != FFM_OK) return e;
     hipLaunchKernelGGL(minmax_grad_kernel, dim3((N + 63) / 64), dim3(64), 0, s, ab_part, mnmx, cnt, gmm, N,
                        SLICE_BWD_BLOCKS);
     FFM_CHECK_LAUNCH();

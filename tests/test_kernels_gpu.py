@@ -708,6 +708,14 @@ def test_casts(ops):
     assert torch.equal(ops.transpose_cast(x, torch.float32), x.t().contiguous())
 
 
+def test_casts_half(ops):
+    """test_casts in IEEE half: the three casts of the half twin (a cast is one rounding, so the results are exact)."""
+    x = rnd(37, 53, seed=43)
+    assert torch.equal(ops.cast_from_f32(x, torch.float16), x.to(torch.float16))
+    assert torch.equal(ops.cast_to_f32(x.to(torch.float16)), x.to(torch.float16).float())
+    assert torch.equal(ops.transpose_cast(x, torch.float16), x.t().contiguous().to(torch.float16))
+
+
 @pytest.mark.parametrize("M,N,K", [(40, 1536, 512), (40, 512, 2048), (40, 2048, 512), (1, 512, 128), (64, 128, 128),
                                    (33, 48, 640), (8, 512, 512)])
 @pytest.mark.parametrize("mode", ["plain", "bias", "bias_res", "bias_gelu", "dgelu"])
@@ -743,6 +751,42 @@ def test_skinny_gemm_text_tower_shapes(M, N, K, mode):
         s = torch.sigmoid(1.702 * x)
         ref = ref * (s * (1 + 1.702 * x * (1 - s)))
     assert rel(out.float(), ref) < 1e-2                              # bf16 rounding of the output only
+
+
+@pytest.mark.parametrize("M,N,K", [(33, 48, 640), (8, 512, 512)], ids=["4waves", "8waves"])
+@pytest.mark.parametrize("mode", ["plain", "bias", "bias_res", "bias_gelu", "dgelu"])
+def test_skinny_gemm_half(M, N, K, mode):
+    """test_skinny_gemm_text_tower_shapes in IEEE half (the half twin of gemm_skinny.hip), at its two smallest shapes that
+    take the four-wave and the eight-wave split of K; fp64 reference on the same half operands, bound tol(float16)."""
+    from fairfedmed_amd import ops
+    dt = torch.float16
+    g = torch.Generator(device="cuda").manual_seed(M * 1000 + N + K)
+    a = (torch.randn(M, K, device="cuda", generator=g)).to(dt)
+    w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).to(dt)
+    bias = torch.randn(N, device="cuda", generator=g)
+    res = torch.randn(M, N, device="cuda", generator=g).to(dt)
+    aux = torch.randn(M, N, device="cuda", generator=g).to(dt)
+    out = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
+    act = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
+    ref = a.double() @ w.double().t()
+    if mode == "plain":
+        ops.gemm_nt(a, w, out)
+    elif mode == "bias":
+        ops.gemm_nt(a, w, out, bias=bias)
+        ref = ref + bias
+    elif mode == "bias_res":
+        ops.gemm_nt(a, w, out, bias=bias, res=res)
+        ref = ref + bias + res.double()
+    elif mode == "bias_gelu":
+        ops.gemm_nt(a, w, out, bias=bias, gelu_out=act)
+        ref = ref + bias
+        check(act, ref * torch.sigmoid(1.702 * ref), tol(dt), "gelu")
+    else:
+        ops.gemm_nt(a, w, out, dgelu_aux=aux)
+        x = aux.double()
+        s = torch.sigmoid(1.702 * x)
+        ref = ref * (s * (1 + 1.702 * x * (1 - s)))
+    check(out, ref, tol(dt), "skinny " + mode)
 
 
 @pytest.mark.parametrize("M,N,K", [(40, 1536, 512), (40, 512, 2048), (40, 2048, 512), (1, 512, 128), (64, 128, 128),
