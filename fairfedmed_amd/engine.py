@@ -20,6 +20,7 @@ epilogue of the dX GEMM, so the dense dW = A diag(s) B is never formed.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -66,7 +67,7 @@ class FlatParams:
         self.optim_desc: Optional[Tensor] = None      # ffm_optim_desc in device memory (fp16 steps / captured steps)
         # optimizer applications ATTEMPTED on the host side.  With the device descriptor (fp16, captured steps) an overflowed
         # step is skipped on the device and optim_desc[9] is the count applied: `steps` is then an upper bound, and
-        # FairLoRAEngine.optim_steps() answers the applied count (SGD only uses `steps == 0` as its first-step flag)
+        # ClipEngine.optim_steps() answers the applied count (SGD only uses `steps == 0` as its first-step flag)
         self.steps = 0
 
     def set_optim_rows(self, rows: int) -> None:
@@ -161,7 +162,7 @@ class SOperands:
 @dataclass(frozen=True)
 class Switches:
     """Every Python-side A/B switch of the engines, read from the environment ONCE, when an engine is constructed
-    (FairLoRAEngine.sw).  The kernel-side switches are the library's own: the table of csrc/switches.h,
+    (ClipEngine.sw).  The kernel-side switches are the library's own: the table of csrc/switches.h,
     read once per process as well and readable through ops.switch (ffm_switch)."""
     red_at: Optional[int] = None           # FFM_RED_AT=0|1|2: where a block's LoRA-gradient reductions start (unset: by row count)
     lgrad: bool = True                     # FFM_LGRAD=0: the two large reductions as launches again, not inside dX(c_proj)
@@ -510,8 +511,38 @@ def _site_bwd(site: Optional[LoraSite], gemm, g, Wt, dx, attr, rps, lgrad=None, 
         site.bwd(g, Wt, dx, attr, rps, gemm=gemm, lgrad=lgrad, down=down, **k)
 
 
-class FairLoRAEngine:
-    """HIP execution engine for CustomCLIP(+FairLoRA) training and inference."""
+class ClipEngine:
+    """HIP execution engine for CustomCLIP(+FairLoRA) training and inference: everything that does not depend on which
+    image tower is attached - the flat parameter buffer, the text tower, the logits and transport heads, the loss, the fp16
+    scale state, streams and events, launch recording and replay, the optimizers and the captured step.  An image tower is
+    a subclass (FairLoRAEngine: ViT, RN50Engine in engine_rn.py) that supplies the hooks below; the base allocates from
+    cfg.vision only `tokens` and `out_dim` (feat, dfeat, rnorm, the head and transport buffers), which every vision
+    config carries.
+
+    The tower contract (TOWER_HOOKS).  A hook without a default raises NotImplementedError here:
+
+      hook                                          called from                                        default
+      _init_vision(max_images)                      __init__, before load_frozen: the tower's          none
+                                                    buffers, its streams and events (ev_layer)
+      _load_vision_frozen(sd, put)                  load_frozen                                        none
+      _init_vision_late()                           __init__, after load_frozen; must leave            none
+                                                    self.sops and self.pack_plan
+      _load_inputs(image, attr, label) -> (b, S)    forward, forward_backward (not replayed)           none
+      _vision_forward(b, S, has_attr, wait=None)    forward, _step_body; ends in _head_forward         none
+      _vision_backward(b, S, has_attr)              _step_body; dfeat -> params.grad                   none
+      _after_plan(b, S)                             forward_backward, between the plan (recorded,      no-op
+                                                    replayed or eager) and unscale_check
+      inference() / infer(image, attr)              trainer, evaluator                                 nullcontext(self) /
+                                                                                                       forward(image, attr),
+                                                                                                       infer_ws None
+
+    A tower that extends the step itself overrides `_step_body` / `forward_backward` and calls super()."""
+
+    # (name, has a default here) of every hook of the contract above, in the table's order
+    TOWER_HOOKS = (("_init_vision", False), ("_load_vision_frozen", False), ("_init_vision_late", False),
+                   ("_load_inputs", False), ("_vision_forward", False), ("_vision_backward", False), ("_after_plan", True),
+                   ("inference", True), ("infer", True))
+    infer_ws = None                                   # a forward-only workspace, where the tower has one
 
     @property
     def grad_scale(self) -> float:
@@ -540,9 +571,9 @@ class FairLoRAEngine:
     def __init__(self, cfg: ModelCfg, state_dict: Dict[str, Tensor], dtype=torch.bfloat16, max_images: int = 32,
                  device: str = "cuda:0", max_infer_images: Optional[int] = None):
         """max_images sizes the training stash (forward / forward_backward), max_infer_images (default: max_images) the
-        depth-independent workspace of the forward-only pass (infer)."""
+        workspace of the forward-only pass (infer) of a tower that has one."""
         if not torch.cuda.is_available():
-            raise RuntimeError("FairLoRAEngine needs an MI355X GPU; there is no CPU path")
+            raise RuntimeError(f"{type(self).__name__} needs an MI355X GPU; there is no CPU path")
         from . import _lib
         _lib.load()                                   # fail loudly if the HIP library is missing
         if cfg.vision.head_dim != 64 or cfg.text.width // cfg.text.heads != 64:
@@ -558,9 +589,6 @@ class FairLoRAEngine:
         self._pack_event = None
         self.pk_out: Dict[str, Tensor] = {}           # frozen weights outside the blocks in MFMA-fragment order
         self.use_replay = True                        # replay recorded launch plans (host-side "graph")
-        # RN50: BatchNorm sums from its own pass instead of the producing GEMM's epilogue (diagnostics assign it) / the
-        # backward sums from the dX products
-        self.no_colstats, self.bn_bwd_fused = False, self.sw.bn_bwd_fused
         self.params = FlatParams(cfg, self.device)
         self.params.load(state_dict)
         self.n_text = cfg.n_prompts * cfg.n_cls
@@ -584,7 +612,7 @@ class FairLoRAEngine:
         self.txt = _Stack(t.width, t.heads, t.layers, self.txt_len, self.n_text, True, 0, torch.float32, self.device,
                           self.sw, x3=(_is16(dtype)))
         dev, f32 = self.device, torch.float32
-        self._init_vision(max_images)                 # tower-specific buffers (ViT here, RN50 in engine_rn.py)
+        self._init_vision(max_images)                 # the tower's buffers (the contract in the class docstring)
         self.load_frozen(state_dict)
         self._init_vision_late()
         self.feat = torch.zeros(max_images * v.tokens, v.out_dim, device=dev, dtype=dtype)
@@ -647,9 +675,6 @@ class FairLoRAEngine:
         # logits head, so it runs on its own HIP stream beside it (forward and backward).
         self.side = self._side0 = torch.cuda.Stream(device=self.device)
         self.grad_stream = self._grad0 = torch.cuda.Stream(device=self.device)
-        self.ev_layer = [torch.cuda.Event() for _ in range(self._n_layer_events())]
-        if Targets.of(cfg.lora).attn:                 # the attention sites' reductions: one more event per block
-            self.ev_attn = [torch.cuda.Event() for _ in range(self._n_layer_events())]
         self.ev_grads = torch.cuda.Event()
         self.ev_tail = torch.cuda.Event()
         self.ev_tail0 = torch.cuda.Event()
@@ -659,85 +684,38 @@ class FairLoRAEngine:
         self.ev_start = torch.cuda.Event()
         self.ev_pack = torch.cuda.Event()
         self.max_infer_images = max_images if max_infer_images is None else int(max_infer_images)
-        self._in_session = False
-        self._init_infer()
 
-    # ---------------------------------------------------- vision tower hooks --
+    # -------------------------------------------------------- tower contract --
     def _init_vision(self, max_images: int) -> None:
-        cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
-        self.vis = _Stack(v.width, v.heads, v.layers, v.tokens, max_images, False, cfg.lora.rank, dtype, dev, self.sw,
-                          targets=Targets.of(cfg.lora))
-        P = v.grid * v.grid
-        self.cols = torch.zeros(max_images * P, 3 * v.patch * v.patch, device=dev, dtype=dtype)
-        self.patch_out = torch.zeros(max_images * P, v.width, device=dev, dtype=dtype)
-        self.hpost = torch.zeros(max_images * v.tokens, v.width, device=dev, dtype=dtype)
-        self.post_stats = (torch.zeros(max_images * v.tokens, device=dev), torch.zeros(max_images * v.tokens, device=dev))
-        f32 = torch.float32
-        self.is3d = cfg.dim_per_3d_slice > 0
-        if self.is3d:
-            D, H = cfg.dim_per_3d_slice, v.image_size
-            nblk = ops.slice_blocks(H, H)
-            self.conv_out = torch.zeros(max_images, 3, H, H, device=dev, dtype=f32)
-            self.dconv = torch.zeros_like(self.conv_out)
-            self.mm_part = torch.zeros(max_images * nblk * 2, device=dev, dtype=f32)
-            self.mnmx = torch.zeros(max_images, 2, device=dev, dtype=f32)
-            self.mm_cnt = torch.zeros(max_images, 2, device=dev, dtype=torch.int32)
-            self.ab_part = torch.zeros(max_images * ops.slice_bwd_ab_blocks() * 2, device=dev, dtype=f32)
-            self.gmm = torch.zeros(max_images, 2, device=dev, dtype=f32)
-            self.wpart = torch.zeros(max_images * ops.slice_wgrad_blocks(H, H) * (3 * D * 25 + 3), device=dev, dtype=f32)
-            self.dcols = torch.zeros_like(self.cols)
-            self.dpatch = torch.zeros_like(self.patch_out)
+        raise NotImplementedError
+
+    def _load_vision_frozen(self, sd: Dict[str, Tensor], put) -> None:
+        raise NotImplementedError
 
     def _init_vision_late(self) -> None:
-        """After the frozen weights are loaded: the tower's LoRA sites and the table that packs their rank operands."""
-        cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
-        ie = "image_encoder.transformer.resblocks."
-        tg = self.vis.targets
-        names = (["attn.in_proj_lora.", "attn.out_proj_lora."] if tg.attn else []) + (["mlp.c_fc.", "mlp.c_proj."] if tg.mlp else [])
-        self.sops = SOperands(self.params, [f"{ie}{i}.{n}" for i in range(v.layers) for n in names], cfg, dev)
-        st, w, r, h16, T = self.vis, v.width, cfg.lora.rank, _is16(dtype), self.vis.max_rows
-        if not r:
-            return
-        for i, blk in enumerate(st.blocks):
-            if tg.mlp:
-                # c_fc has ln_2 folded into it (Route.ln2): its rank operand gamma-scaled too, and - ln_2's backward fold
-                # (Route.ln2_bwd) - the rank operand of dX(c_fc) carries W gamma and W beta + b as rows 14 / 15: its t[14] / t[15]
-                # are the two row sums against those vectors, out of the matrix cores; every consumer masks the slots beyond r
-                fc = LoraSite(self, f"{ie}{i}.mlp.c_fc.", w, 4 * w, T, u=st.u, wide=h16, ln=(blk.ln2_w, blk.ln2_b) if h16 else None,
-                              row1415=(blk.c_fc, blk.d_fc) if (h16 and blk.c_fc is not None and r <= 14) else None)
-                proj = LoraSite(self, f"{ie}{i}.mlp.c_proj.", 4 * w, w, T, u=st.u, wide=h16)
-                st.sites.append((fc, proj))
-            if tg.attn:
-                # the in-projection takes ln_1 folded into the qkv product (Route.ln1) as c_fc takes ln_2; ln_1's backward
-                # is never folded for it (tower_route), so its dX product carries no row sums
-                ain = LoraSite(self, f"{ie}{i}.attn.in_proj_lora.", w, 3 * w, T, u=st.u, wide=h16,
-                               ln=(blk.ln1_w, blk.ln1_b) if h16 else None)
-                aout = LoraSite(self, f"{ie}{i}.attn.out_proj_lora.", w, w, T, u=st.u, wide=h16)
-                st.asites.append((ain, aout))
-        # dS partials: one size for the tower, the largest of ffm_lora_down's blocks and of the row tiles of either kernel
-        # ffm_gemm_nt may pick for the dX products (c_proj's carries the dGELU)
-        last = (st.sites[-1] if tg.mlp else ()) + (st.asites[-1] if tg.attn else ())
-        nb = max([ops.lora_down_blocks_max(T, s.N, r, dtype) for s in last]
-                 + [s.ds_tiles(T, p, dgelu=s.prefix.endswith("mlp.c_proj.")) for s in last for p in (False, True)])
-        for s in (s for pair in st.sites + st.asites for s in pair):
-            s.alloc_ds(nb * 8 * r)
-        if self.fused_rank:
-            # one table for all blocks, in the order (fc A, proj A, fc B, proj B, fc A with ln_2) per block; behind them the
-            # attention sites' (in A, out A, in B, out B, in A with ln_1) per block
-            ent = []
-            for fc, proj in st.sites + st.asites:
-                (fa, fb, *fln), (pa, pb) = fc.pack_entries(), proj.pack_entries()
-                ent += [fa, pa, fb, pb, *fln]
-            self.pack_plan = ops.PackPlan(ent, dtype, dev)
+        raise NotImplementedError
 
-    def _init_infer(self) -> None:
-        """The evaluation pass's workspace (RN50: none, engine_rn.py)."""
-        if self.max_infer_images < 1:
-            raise ValueError(f"max_infer_images must be positive, got {self.max_infer_images}")
-        self.infer_ws = _InferWorkspace(self, self.max_infer_images)
+    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor]) -> Tuple[int, int]:
+        raise NotImplementedError
 
-    def _n_layer_events(self) -> int:
-        return self.cfg.vision.layers
+    def _vision_forward(self, b: int, S: int, has_attr: bool, wait=None) -> None:
+        raise NotImplementedError
+
+    def _vision_backward(self, b: int, S: int, has_attr: bool) -> None:
+        raise NotImplementedError
+
+    def _after_plan(self, b: int, S: int) -> None:
+        """What a step launches outside its plan, behind it: it may read the caller's tensors (no static address) and writes
+        params.grad in front of unscale_check."""
+
+    def inference(self):
+        """``with eng.inference():`` - an evaluation session.  Without a forward-only pass a session changes nothing, so
+        that a trainer treats every tower alike."""
+        return contextlib.nullcontext(self)
+
+    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
+        """forward()'s logits [B, n_cls]; a tower with a forward-only pass overrides it."""
+        return self.forward(image, attr)
 
     # ------------------------------------------------------------ weights --
     def _w(self, x: Tensor, dtype=None) -> Tensor:
@@ -816,27 +794,6 @@ class FairLoRAEngine:
         put("txt_pos", self._f(sd[te + "positional_embedding"]))
         put("lnfinal", (self._f(sd[te + "ln_final.weight"]), self._f(sd[te + "ln_final.bias"])))
         put("text_proj", self._f(sd[te + "text_projection"]))
-
-    def _load_vision_frozen(self, sd: Dict[str, Tensor], put) -> None:
-        cfg, v = self.cfg, self.cfg.vision
-        ie = "image_encoder."
-        self._load_stack(self.vis, sd, ie, True)
-        put("conv_w", self._w(sd[ie + "conv1.weight"].reshape(v.width, -1)))
-        if cfg.dim_per_3d_slice:
-            put("conv_w_t", self._wt(sd[ie + "conv1.weight"].reshape(v.width, -1)))   # dX of the patch embedding
-        put("cls", self._w(sd[ie + "class_embedding"]))
-        put("pos", self._w(sd[ie + "positional_embedding"]))
-        put("lnpre", (self._f(sd[ie + "ln_pre.weight"]), self._f(sd[ie + "ln_pre.bias"])))
-        put("lnpost", (self._f(sd[ie + "ln_post.weight"]), self._f(sd[ie + "ln_post.bias"])))
-        put("proj", self._w(sd[ie + "proj"]))                     # [width, out]: B operand of dh = df proj^T
-        put("proj_t", self._wt(sd[ie + "proj"]))                  # [out, width]: B operand of f = h proj
-        # the three frozen weights outside the blocks in MFMA-fragment order too (16-bit modes): patch embedding and the
-        # two products of the final projection take the panel kernel where their shape fills the chip
-        if _is16(self.dtype) and self.sw.pack_out:
-            for name in ("conv_w", "proj", "proj_t"):
-                w = getattr(self, name)
-                if w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0:
-                    self.pk_out[name] = ops.pack_b(w, self.pk_out.get(name))
 
     # -------------------------------------------------------------- tower --
     def _stack_forward(self, st: _Stack, rows: int, images: int, attr: Optional[Tensor], rows_per_sample: int,
@@ -1119,7 +1076,7 @@ class FairLoRAEngine:
         self._stack_backward(self.txt, rows, self.n_text, None, self.txt_len, True)
         ops.text_ctx_grad(self.txt.g, self.params.view("prompt_learner.ctx", "grad"), cfg.n_cls, self.txt_len)
 
-    # ------------------------------------------------------------- vision --
+    # ---------------------------------- the ends every image tower shares --
     def _as_f32(self, image: Tensor, slot: str = "_u8_stage") -> Tensor:
         """uint8 transport (fairfedmed_amd.data, transport="uint8"): expand on the GPU to the float32 batch the
         reference's loader ships - a single SLO / X-ray channel is repeated to 3 (utils/data_utils.py:676-679).  A
@@ -1146,79 +1103,6 @@ class FairLoRAEngine:
         if native:
             return ops.resize_u8(image, stage[:b])
         return ops.expand_u8(image.contiguous(), stage[:b], rep)
-
-    def _check_batch(self, image: Tensor, limit: Optional[int] = None, what: str = "max_images") -> Tuple[int, int]:
-        cfg, v = self.cfg, self.cfg.vision
-        limit = self.max_images if limit is None else limit
-        if not image.is_cuda or image.dtype != torch.float32:
-            raise TypeError("image must be a float32 CUDA tensor of raw 0..255 values")
-        b, c, h, w = image.shape
-        D = cfg.dim_per_3d_slice
-        if h != v.image_size or w != v.image_size or (not D and c != 3) or (D and c % D):
-            raise ValueError(f"expected [B,{'S*%d' % D if D else 3},{v.image_size},{v.image_size}], "
-                             f"got {tuple(image.shape)}")
-        S = c // D if D else 1                       # slices per sample: the ViT batch is b*S (:683-684)
-        if b * S > limit:
-            raise ValueError(f"{b * S} ViT images exceed the engine's {what}={limit}")
-        return b, S
-
-    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor], ws=None):
-        """Per-step inputs -> static buffers (these three launches are the only ones not replayed).  ws: the evaluation
-        pass's workspace instead of the engine's own (training) buffers."""
-        cfg, v = self.cfg, self.cfg.vision
-        if ws is None:
-            image = self._as_f32(image)
-            b, S = self._check_batch(image)
-            ws = self
-        else:
-            image = self._as_f32(image, "_u8_stage_infer")
-            b, S = self._check_batch(image, ws.max_images, "max_infer_images")
-        images = b * S
-        P = v.grid * v.grid
-        if self.is3d:
-            # trainable 5x5 slice conv + per-image min-max (trainers/GLP_OT_SVLoRA.py:681-690), then the patches
-            image = image.contiguous()
-            if ws is self:
-                self._image = image                   # (the backward of the slice convolution reads it)
-            ops.slice_conv_fwd(image, self.params.view("proj_per_3d_slice.weight"),
-                               self.params.view("proj_per_3d_slice.bias"), ws.conv_out[:images], ws.mm_part,
-                               ws.mnmx, ws.mm_cnt, cfg.dim_per_3d_slice)
-            ops.patchify_minmax(ws.conv_out[:images], ws.mnmx, ws.mm_cnt, ws.cols[:images * P], v.patch,
-                                cfg.pixel_mean, cfg.pixel_std)
-        else:
-            ops.patchify(image.contiguous(), ws.cols[:images * P], v.patch, cfg.pixel_mean, cfg.pixel_std)
-        if attr is not None:
-            ws.attr_i32[:b].copy_(attr)
-        if label is not None:
-            self.label_buf[:b].copy_(label)
-        return b, S
-
-    def _vision_forward(self, b: int, S: int, has_attr: bool, wait=None, ws=None) -> None:
-        """Patch embedding -> tower -> ln_post, projection -> logits head.  ws None: on the engine's own buffers and the
-        tower's stash (training, forward()), S_eff and the rank operands refreshed on the way.  ws an `_InferWorkspace`: the
-        same launches on the workspace; whoever calls has refreshed S_eff and the rank operands (infer / inference)."""
-        cfg, v = self.cfg, self.cfg.vision
-        images = b * S
-        P, L = v.grid * v.grid, v.tokens
-        rows = images * L
-        train = ws is None
-        ws = self if train else ws
-        bufs = self.vis if train else ws
-        a32 = ws.attr_i32[:b] if has_attr else None
-        if train and self.sops.glob:
-            self._glue(self.sops.prepare)             # S_eff = S + S_global
-        ops.gemm_nt(ws.cols[:images * P], self.conv_w, ws.patch_out[:images * P], b_packed=self.pk_out.get("conv_w"))
-        lb0 = bufs.layer(0, rows)
-        ops.embed_lnpre(ws.patch_out[:images * P], self.cls, self.pos, self.lnpre[0], self.lnpre[1],
-                        lb0.x, images, L, rowstat=lb0.rowp)
-        if train:
-            self._rank_operands_ready()               # LoRA matrices -> GEMM rank operands (they change every step)
-        out = self._stack_forward(self.vis, rows, images, a32, L * S, bufs)
-        ops.layernorm_fwd(out, ws.hpost[:rows], self.lnpost[0], self.lnpost[1], ws.post_stats[0], ws.post_stats[1])
-        ops.gemm_nt(ws.hpost[:rows], self.proj_t, ws.feat[:rows], b_packed=self.pk_out.get("proj_t"))
-        if wait is not None:
-            self._ev_wait(torch.cuda.current_stream(self.device), wait)     # text features ready
-        self._head_forward(rows, images, L, ws)
 
     def _pack_rank_operands(self) -> None:
         """ffm_lora_pack_multi over every adapter (one or two launches) on the CURRENT stream."""
@@ -1256,25 +1140,6 @@ class FairLoRAEngine:
             ops.head_bwd(self.feat[:rows], self.tbar_buf, self.logit_scale, self.fbar, self.rnorm, self.dlogits_img,
                          self.dfeat[:rows], self.dtbar, images, L, cfg.n_cls)
 
-    def _vision_backward(self, b: int, S: int, has_attr: bool) -> None:
-        """dfeat -> gradients of every trainable tensor of the image side (params.grad)."""
-        cfg, v = self.cfg, self.cfg.vision
-        images, L = b * S, v.tokens
-        rows = images * L
-        a32 = self.attr_i32[:b] if has_attr else None
-        ops.gemm_nt(self.dfeat[:rows], self.proj, self.vis.dh[:rows], b_packed=self.pk_out.get("proj"))
-        # (straight into the buffer the last block's LoRA-gradient reductions read: no copy on the main stream)
-        gl = bool(self.vis.sites)
-        ops.layernorm_bwd(self.vis.dh[:rows], self.vis.x[v.layers][:rows], self.lnpost[0], self.post_stats[0],
-                          self.post_stats[1], None, (self.vis.g_l[v.layers - 1] if gl else self.vis.g)[:rows])
-        self._stack_backward(self.vis, rows, images, a32, L * S, self.is3d, grad_in_last=gl)
-        if self.is3d:
-            # dL/d(tokens) -> ln_pre / pos-add backward -> dX of the patch embedding (columns of the patches)
-            P = v.grid * v.grid
-            ops.embed_lnpre_bwd(self.vis.g[:rows], self.patch_out[:images * P], self.pos, self.lnpre[0],
-                                self.dpatch[:images * P], images, L)
-            ops.gemm_nt(self.dpatch[:images * P], self.conv_w_t, self.dcols[:images * P])
-
     # ---------------------------------------------------------------- API --
     @torch.no_grad()
     def forward(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
@@ -1285,49 +1150,6 @@ class FairLoRAEngine:
         self._text_forward(False)
         self._vision_forward(b, S, attr is not None)
         return self.logits_img[:b * S].view(b, S, -1).mean(1)
-
-    def _infer_prepare(self) -> None:
-        """What an evaluation needs from the CURRENT parameters besides the vision pass: the rank operands of the FairLoRA
-        products, S_eff (GLOBAL_S) and the text features."""
-        self._pack_rank_operands()
-        if self.sops.glob:
-            self.sops.prepare()
-        self._text_forward(False)
-
-    def inference(self):
-        """``with eng.inference():`` - an evaluation session.  On entry the rank operands are packed from the current
-        parameters, S_eff is refreshed and the text tower runs ONCE; inside, `infer` runs the vision tower and the head
-        only.  The session is the contract: the parameters must not be stepped (sgd_step, a captured step, load) inside it -
-        nothing looks for stale operands.  Sessions do not nest usefully (an inner one prepares again)."""
-        eng = self
-
-        class _Session:
-            def __enter__(self):
-                with torch.no_grad():
-                    eng._infer_prepare()
-                self.prev, eng._in_session = eng._in_session, True
-                return eng
-
-            def __exit__(self, *a):
-                eng._in_session = self.prev
-                return False
-        return _Session()
-
-    @torch.no_grad()
-    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
-        """forward()'s logits [B, n_cls], bit for bit, by the forward-only pass: the same launches in the same order on the
-        inference workspace (up to max_infer_images ViT images), with nothing stored for a backward pass - c_fc leaves the
-        activation alone (FFM_EPI_GELU_ONLY), no rank vectors, no log-sum-exp, no LayerNorm statistics.  Gradients,
-        momentum, the training stash, the step-count buffers, the fp16 scale state and a captured training step are not
-        touched.  Outside an `inference()` session every call prepares the rank operands and the text features itself."""
-        if self.sops.type != "FairLoRA":
-            attr = None                               # LoRALinear / SVLoRALinear.forward ignore attr (:241, :307)
-        ws = self.infer_ws
-        b, S = self._load_inputs(image, attr, None, ws)
-        if not self._in_session:
-            self._infer_prepare()
-        self._vision_forward(b, S, attr is not None, ws=ws)
-        return ws.logits_img[:b * S].view(b, S, -1).mean(1)
 
     def _step_body(self, b: int, S: int, has_attr: bool) -> None:
         cfg, v = self.cfg, self.cfg.vision
@@ -1398,16 +1220,7 @@ class FairLoRAEngine:
                 self.step_plans[key] = plan
             else:
                 self._step_body(b, S, attr is not None)
-            if self.is3d:
-                images, P, D = b * S, self.cfg.vision.grid ** 2, self.cfg.dim_per_3d_slice
-                ops.slice_bwd(self.dcols[:images * P], self._image, self.conv_out[:images], self.mnmx, self.mm_cnt,
-                              self.dconv[:images], self.ab_part, self.gmm, self.wpart, D, self.cfg.vision.patch,
-                              self.cfg.pixel_std)
-                nw = 3 * D * 25 + 3
-                off = self.params.offsets["proj_per_3d_slice.weight"][0]
-                assert self.params.offsets["proj_per_3d_slice.bias"][0] == off + nw - 3
-                nblk = ops.slice_wgrad_blocks(self.cfg.vision.image_size, self.cfg.vision.image_size)
-                ops.reduce_partials(self.wpart, images * nblk, nw, self.params.grad[off:off + nw])
+            self._after_plan(b, S)
             if self.scale_state is not None:
                 ops.unscale_check(self.params.grad, self.scale_state)
         out = {"loss": self.loss, "logits": self.logits[:b], "prob": self.prob[:b], "finite": self.finite}
@@ -1519,11 +1332,276 @@ class FairLoRAEngine:
         return {k: self.params.view(k) for k in self.params.keys}
 
 
+class FairLoRAEngine(ClipEngine):
+    """ClipEngine with CLIP's VisionTransformer as the image tower: patch embedding (behind the 3D slice front end, where
+    the config has one), the `_Stack` of vision blocks, ln_post and the projection - and the forward-only pass (`infer`) on a
+    workspace of its own."""
+
+    def __init__(self, cfg: ModelCfg, state_dict: Dict[str, Tensor], dtype=torch.bfloat16, max_images: int = 32,
+                 device: str = "cuda:0", max_infer_images: Optional[int] = None):
+        """max_infer_images (default: max_images) sizes the depth-independent workspace of the forward-only pass (infer)."""
+        super().__init__(cfg, state_dict, dtype, max_images, device, max_infer_images)
+        self._in_session = False
+        self._init_infer()
+
+    # ----------------------------------------------------------------- setup --
+    def _init_vision(self, max_images: int) -> None:
+        cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
+        self.vis = _Stack(v.width, v.heads, v.layers, v.tokens, max_images, False, cfg.lora.rank, dtype, dev, self.sw,
+                          targets=Targets.of(cfg.lora))
+        P = v.grid * v.grid
+        self.cols = torch.zeros(max_images * P, 3 * v.patch * v.patch, device=dev, dtype=dtype)
+        self.patch_out = torch.zeros(max_images * P, v.width, device=dev, dtype=dtype)
+        self.hpost = torch.zeros(max_images * v.tokens, v.width, device=dev, dtype=dtype)
+        self.post_stats = (torch.zeros(max_images * v.tokens, device=dev), torch.zeros(max_images * v.tokens, device=dev))
+        f32 = torch.float32
+        self.is3d = cfg.dim_per_3d_slice > 0
+        if self.is3d:
+            D, H = cfg.dim_per_3d_slice, v.image_size
+            nblk = ops.slice_blocks(H, H)
+            self.conv_out = torch.zeros(max_images, 3, H, H, device=dev, dtype=f32)
+            self.dconv = torch.zeros_like(self.conv_out)
+            self.mm_part = torch.zeros(max_images * nblk * 2, device=dev, dtype=f32)
+            self.mnmx = torch.zeros(max_images, 2, device=dev, dtype=f32)
+            self.mm_cnt = torch.zeros(max_images, 2, device=dev, dtype=torch.int32)
+            self.ab_part = torch.zeros(max_images * ops.slice_bwd_ab_blocks() * 2, device=dev, dtype=f32)
+            self.gmm = torch.zeros(max_images, 2, device=dev, dtype=f32)
+            self.wpart = torch.zeros(max_images * ops.slice_wgrad_blocks(H, H) * (3 * D * 25 + 3), device=dev, dtype=f32)
+            self.dcols = torch.zeros_like(self.cols)
+            self.dpatch = torch.zeros_like(self.patch_out)
+        # _stack_backward: one event per block for its MLP sites' reductions, one more for the attention sites'
+        self.ev_layer = [torch.cuda.Event() for _ in range(v.layers)]
+        if Targets.of(cfg.lora).attn:
+            self.ev_attn = [torch.cuda.Event() for _ in range(v.layers)]
+
+    def _init_vision_late(self) -> None:
+        """After the frozen weights are loaded: the tower's LoRA sites and the table that packs their rank operands."""
+        cfg, v, dtype, dev = self.cfg, self.cfg.vision, self.dtype, self.device
+        ie = "image_encoder.transformer.resblocks."
+        tg = self.vis.targets
+        names = (["attn.in_proj_lora.", "attn.out_proj_lora."] if tg.attn else []) + (["mlp.c_fc.", "mlp.c_proj."] if tg.mlp else [])
+        self.sops = SOperands(self.params, [f"{ie}{i}.{n}" for i in range(v.layers) for n in names], cfg, dev)
+        st, w, r, h16, T = self.vis, v.width, cfg.lora.rank, _is16(dtype), self.vis.max_rows
+        if not r:
+            return
+        for i, blk in enumerate(st.blocks):
+            if tg.mlp:
+                # c_fc has ln_2 folded into it (Route.ln2): its rank operand gamma-scaled too, and - ln_2's backward fold
+                # (Route.ln2_bwd) - the rank operand of dX(c_fc) carries W gamma and W beta + b as rows 14 / 15: its t[14] / t[15]
+                # are the two row sums against those vectors, out of the matrix cores; every consumer masks the slots beyond r
+                fc = LoraSite(self, f"{ie}{i}.mlp.c_fc.", w, 4 * w, T, u=st.u, wide=h16, ln=(blk.ln2_w, blk.ln2_b) if h16 else None,
+                              row1415=(blk.c_fc, blk.d_fc) if (h16 and blk.c_fc is not None and r <= 14) else None)
+                proj = LoraSite(self, f"{ie}{i}.mlp.c_proj.", 4 * w, w, T, u=st.u, wide=h16)
+                st.sites.append((fc, proj))
+            if tg.attn:
+                # the in-projection takes ln_1 folded into the qkv product (Route.ln1) as c_fc takes ln_2; ln_1's backward
+                # is never folded for it (tower_route), so its dX product carries no row sums
+                ain = LoraSite(self, f"{ie}{i}.attn.in_proj_lora.", w, 3 * w, T, u=st.u, wide=h16,
+                               ln=(blk.ln1_w, blk.ln1_b) if h16 else None)
+                aout = LoraSite(self, f"{ie}{i}.attn.out_proj_lora.", w, w, T, u=st.u, wide=h16)
+                st.asites.append((ain, aout))
+        # dS partials: one size for the tower, the largest of ffm_lora_down's blocks and of the row tiles of either kernel
+        # ffm_gemm_nt may pick for the dX products (c_proj's carries the dGELU)
+        last = (st.sites[-1] if tg.mlp else ()) + (st.asites[-1] if tg.attn else ())
+        nb = max([ops.lora_down_blocks_max(T, s.N, r, dtype) for s in last]
+                 + [s.ds_tiles(T, p, dgelu=s.prefix.endswith("mlp.c_proj.")) for s in last for p in (False, True)])
+        for s in (s for pair in st.sites + st.asites for s in pair):
+            s.alloc_ds(nb * 8 * r)
+        if self.fused_rank:
+            # one table for all blocks, in the order (fc A, proj A, fc B, proj B, fc A with ln_2) per block; behind them the
+            # attention sites' (in A, out A, in B, out B, in A with ln_1) per block
+            ent = []
+            for fc, proj in st.sites + st.asites:
+                (fa, fb, *fln), (pa, pb) = fc.pack_entries(), proj.pack_entries()
+                ent += [fa, pa, fb, pb, *fln]
+            self.pack_plan = ops.PackPlan(ent, dtype, dev)
+
+    def _init_infer(self) -> None:
+        """The evaluation pass's workspace."""
+        if self.max_infer_images < 1:
+            raise ValueError(f"max_infer_images must be positive, got {self.max_infer_images}")
+        self.infer_ws = _InferWorkspace(self, self.max_infer_images)
+
+    def _load_vision_frozen(self, sd: Dict[str, Tensor], put) -> None:
+        cfg, v = self.cfg, self.cfg.vision
+        ie = "image_encoder."
+        self._load_stack(self.vis, sd, ie, True)
+        put("conv_w", self._w(sd[ie + "conv1.weight"].reshape(v.width, -1)))
+        if cfg.dim_per_3d_slice:
+            put("conv_w_t", self._wt(sd[ie + "conv1.weight"].reshape(v.width, -1)))   # dX of the patch embedding
+        put("cls", self._w(sd[ie + "class_embedding"]))
+        put("pos", self._w(sd[ie + "positional_embedding"]))
+        put("lnpre", (self._f(sd[ie + "ln_pre.weight"]), self._f(sd[ie + "ln_pre.bias"])))
+        put("lnpost", (self._f(sd[ie + "ln_post.weight"]), self._f(sd[ie + "ln_post.bias"])))
+        put("proj", self._w(sd[ie + "proj"]))                     # [width, out]: B operand of dh = df proj^T
+        put("proj_t", self._wt(sd[ie + "proj"]))                  # [out, width]: B operand of f = h proj
+        # the three frozen weights outside the blocks in MFMA-fragment order too (16-bit modes): patch embedding and the
+        # two products of the final projection take the panel kernel where their shape fills the chip
+        if _is16(self.dtype) and self.sw.pack_out:
+            for name in ("conv_w", "proj", "proj_t"):
+                w = getattr(self, name)
+                if w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0:
+                    self.pk_out[name] = ops.pack_b(w, self.pk_out.get(name))
+
+    # ---------------------------------------------------------------- inputs --
+    def _check_batch(self, image: Tensor, limit: Optional[int] = None, what: str = "max_images") -> Tuple[int, int]:
+        cfg, v = self.cfg, self.cfg.vision
+        limit = self.max_images if limit is None else limit
+        if not image.is_cuda or image.dtype != torch.float32:
+            raise TypeError("image must be a float32 CUDA tensor of raw 0..255 values")
+        b, c, h, w = image.shape
+        D = cfg.dim_per_3d_slice
+        if h != v.image_size or w != v.image_size or (not D and c != 3) or (D and c % D):
+            raise ValueError(f"expected [B,{'S*%d' % D if D else 3},{v.image_size},{v.image_size}], "
+                             f"got {tuple(image.shape)}")
+        S = c // D if D else 1                       # slices per sample: the ViT batch is b*S (:683-684)
+        if b * S > limit:
+            raise ValueError(f"{b * S} ViT images exceed the engine's {what}={limit}")
+        return b, S
+
+    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor], ws=None) -> Tuple[int, int]:
+        """Per-step inputs -> static buffers (these three launches are the only ones not replayed).  ws: the evaluation
+        pass's workspace instead of the engine's own (training) buffers."""
+        cfg, v = self.cfg, self.cfg.vision
+        if ws is None:
+            image = self._as_f32(image)
+            b, S = self._check_batch(image)
+            ws = self
+        else:
+            image = self._as_f32(image, "_u8_stage_infer")
+            b, S = self._check_batch(image, ws.max_images, "max_infer_images")
+        images = b * S
+        P = v.grid * v.grid
+        if self.is3d:
+            # trainable 5x5 slice conv + per-image min-max (trainers/GLP_OT_SVLoRA.py:681-690), then the patches
+            image = image.contiguous()
+            if ws is self:
+                self._image = image                   # (the backward of the slice convolution reads it)
+            ops.slice_conv_fwd(image, self.params.view("proj_per_3d_slice.weight"),
+                               self.params.view("proj_per_3d_slice.bias"), ws.conv_out[:images], ws.mm_part,
+                               ws.mnmx, ws.mm_cnt, cfg.dim_per_3d_slice)
+            ops.patchify_minmax(ws.conv_out[:images], ws.mnmx, ws.mm_cnt, ws.cols[:images * P], v.patch,
+                                cfg.pixel_mean, cfg.pixel_std)
+        else:
+            ops.patchify(image.contiguous(), ws.cols[:images * P], v.patch, cfg.pixel_mean, cfg.pixel_std)
+        if attr is not None:
+            ws.attr_i32[:b].copy_(attr)
+        if label is not None:
+            self.label_buf[:b].copy_(label)
+        return b, S
+
+    # ---------------------------------------------------------------- forward --
+    def _vision_forward(self, b: int, S: int, has_attr: bool, wait=None, ws=None) -> None:
+        """Patch embedding -> tower -> ln_post, projection -> logits head.  ws None: on the engine's own buffers and the
+        tower's stash (training, forward()), S_eff and the rank operands refreshed on the way.  ws an `_InferWorkspace`: the
+        same launches on the workspace; whoever calls has refreshed S_eff and the rank operands (infer / inference)."""
+        cfg, v = self.cfg, self.cfg.vision
+        images = b * S
+        P, L = v.grid * v.grid, v.tokens
+        rows = images * L
+        train = ws is None
+        ws = self if train else ws
+        bufs = self.vis if train else ws
+        a32 = ws.attr_i32[:b] if has_attr else None
+        if train and self.sops.glob:
+            self._glue(self.sops.prepare)             # S_eff = S + S_global
+        ops.gemm_nt(ws.cols[:images * P], self.conv_w, ws.patch_out[:images * P], b_packed=self.pk_out.get("conv_w"))
+        lb0 = bufs.layer(0, rows)
+        ops.embed_lnpre(ws.patch_out[:images * P], self.cls, self.pos, self.lnpre[0], self.lnpre[1],
+                        lb0.x, images, L, rowstat=lb0.rowp)
+        if train:
+            self._rank_operands_ready()               # LoRA matrices -> GEMM rank operands (they change every step)
+        out = self._stack_forward(self.vis, rows, images, a32, L * S, bufs)
+        ops.layernorm_fwd(out, ws.hpost[:rows], self.lnpost[0], self.lnpost[1], ws.post_stats[0], ws.post_stats[1])
+        ops.gemm_nt(ws.hpost[:rows], self.proj_t, ws.feat[:rows], b_packed=self.pk_out.get("proj_t"))
+        if wait is not None:
+            self._ev_wait(torch.cuda.current_stream(self.device), wait)     # text features ready
+        self._head_forward(rows, images, L, ws)
+
+    # --------------------------------------------------------------- backward --
+    def _vision_backward(self, b: int, S: int, has_attr: bool) -> None:
+        """dfeat -> gradients of every trainable tensor of the image side (params.grad)."""
+        cfg, v = self.cfg, self.cfg.vision
+        images, L = b * S, v.tokens
+        rows = images * L
+        a32 = self.attr_i32[:b] if has_attr else None
+        ops.gemm_nt(self.dfeat[:rows], self.proj, self.vis.dh[:rows], b_packed=self.pk_out.get("proj"))
+        # (straight into the buffer the last block's LoRA-gradient reductions read: no copy on the main stream)
+        gl = bool(self.vis.sites)
+        ops.layernorm_bwd(self.vis.dh[:rows], self.vis.x[v.layers][:rows], self.lnpost[0], self.post_stats[0],
+                          self.post_stats[1], None, (self.vis.g_l[v.layers - 1] if gl else self.vis.g)[:rows])
+        self._stack_backward(self.vis, rows, images, a32, L * S, self.is3d, grad_in_last=gl)
+        if self.is3d:
+            # dL/d(tokens) -> ln_pre / pos-add backward -> dX of the patch embedding (columns of the patches)
+            P = v.grid * v.grid
+            ops.embed_lnpre_bwd(self.vis.g[:rows], self.patch_out[:images * P], self.pos, self.lnpre[0],
+                                self.dpatch[:images * P], images, L)
+            ops.gemm_nt(self.dpatch[:images * P], self.conv_w_t, self.dcols[:images * P])
+
+    def _after_plan(self, b: int, S: int) -> None:
+        """The 3D front end's tail: the slice convolution's backward reads the caller's image (`_image`), so it is launched
+        on every step, not replayed."""
+        if self.is3d:
+            images, P, D = b * S, self.cfg.vision.grid ** 2, self.cfg.dim_per_3d_slice
+            ops.slice_bwd(self.dcols[:images * P], self._image, self.conv_out[:images], self.mnmx, self.mm_cnt,
+                          self.dconv[:images], self.ab_part, self.gmm, self.wpart, D, self.cfg.vision.patch,
+                          self.cfg.pixel_std)
+            nw = 3 * D * 25 + 3
+            off = self.params.offsets["proj_per_3d_slice.weight"][0]
+            assert self.params.offsets["proj_per_3d_slice.bias"][0] == off + nw - 3
+            nblk = ops.slice_wgrad_blocks(self.cfg.vision.image_size, self.cfg.vision.image_size)
+            ops.reduce_partials(self.wpart, images * nblk, nw, self.params.grad[off:off + nw])
+
+    # -------------------------------------------------------------- evaluation --
+    def _infer_prepare(self) -> None:
+        """What an evaluation needs from the CURRENT parameters besides the vision pass: the rank operands of the FairLoRA
+        products, S_eff (GLOBAL_S) and the text features."""
+        self._pack_rank_operands()
+        if self.sops.glob:
+            self.sops.prepare()
+        self._text_forward(False)
+
+    def inference(self):
+        """``with eng.inference():`` - an evaluation session.  On entry the rank operands are packed from the current
+        parameters, S_eff is refreshed and the text tower runs ONCE; inside, `infer` runs the vision tower and the head
+        only.  The session is the contract: the parameters must not be stepped (sgd_step, a captured step, load) inside it -
+        nothing looks for stale operands.  Sessions do not nest usefully (an inner one prepares again)."""
+        eng = self
+
+        class _Session:
+            def __enter__(self):
+                with torch.no_grad():
+                    eng._infer_prepare()
+                self.prev, eng._in_session = eng._in_session, True
+                return eng
+
+            def __exit__(self, *a):
+                eng._in_session = self.prev
+                return False
+        return _Session()
+
+    @torch.no_grad()
+    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
+        """forward()'s logits [B, n_cls], bit for bit, by the forward-only pass: the same launches in the same order on the
+        inference workspace (up to max_infer_images ViT images), with nothing stored for a backward pass - c_fc leaves the
+        activation alone (FFM_EPI_GELU_ONLY), no rank vectors, no log-sum-exp, no LayerNorm statistics.  Gradients,
+        momentum, the training stash, the step-count buffers, the fp16 scale state and a captured training step are not
+        touched.  Outside an `inference()` session every call prepares the rank operands and the text features itself."""
+        if self.sops.type != "FairLoRA":
+            attr = None                               # LoRALinear / SVLoRALinear.forward ignore attr (:241, :307)
+        ws = self.infer_ws
+        b, S = self._load_inputs(image, attr, None, ws=ws)
+        if not self._in_session:
+            self._infer_prepare()
+        self._vision_forward(b, S, attr is not None, ws=ws)
+        return ws.logits_img[:b * S].view(b, S, -1).mean(1)
+
+
 class GraphedStep:
     """One captured training step.  ``run(image, attr, label)`` copies the batch into the static input
     buffers and replays the graph; results are the engine's usual device tensors (loss, logits, prob, finite)."""
 
-    def __init__(self, eng: FairLoRAEngine, batch_size: int, lr: float, momentum: float, weight_decay: float,
+    def __init__(self, eng: ClipEngine, batch_size: int, lr: float, momentum: float, weight_decay: float,
                  repeats: int = 1, optimizer=None):
         if not 1 <= repeats <= 16:
             raise ValueError(f"repeats must be 1..16, got {repeats}")

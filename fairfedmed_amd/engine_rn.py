@@ -10,7 +10,8 @@ so every 1x1 convolution IS ffm_gemm_nt on the rows (with the FairLoRA epilogue)
 3x3 convolutions are an implicit GEMM (ffm_conv3x3_nhwc: the GEMM's A loader reads the patch from the
 neighbouring pixels, weight re-ordered once to [Cout, (ky, kx, cin)]; the input gradient is the same call on dY), and the attention pool runs on [image*L, E] token rows with
 the ViT attention kernels (head_dim 64, 32 heads).  The text tower, logits head,
-flat parameter buffer, SGD, streams and launch-plan replay are the base class's.
+flat parameter buffer, SGD, streams and launch-plan replay are the base class's
+(ClipEngine, whose docstring holds the hooks a tower supplies); the ViT engine is a sibling.
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import torch
 
 from . import ops
 from ._lib import is16 as _is16
-from .engine import FairLoRAEngine, SOperands, _round_up
+from .engine import ClipEngine, FairLoRAEngine, SOperands, _round_up
 from .lora_site import LoraSite
 from .synth import buffer_keys
 
@@ -270,8 +271,9 @@ class _Bneck:
         return [(self.c1, self.Hin), (self.c3, self.Hout)]
 
 
-class RN50Engine(FairLoRAEngine):
-    """FairLoRAEngine with CLIP's ModifiedResNet as the image tower."""
+class RN50Engine(ClipEngine):
+    """ClipEngine with CLIP's ModifiedResNet as the image tower.  It has no forward-only pass yet: `infer` is forward()
+    (eval-mode BatchNorm as there) and an `inference()` session changes nothing - the base's defaults."""
 
     # ------------------------------------------------------------------ setup --
     def _init_vision(self, max_images: int) -> None:
@@ -280,8 +282,9 @@ class RN50Engine(FairLoRAEngine):
             raise ValueError("the 3D OCT front end is built for the ViT tower only")
         if v.image_size % 32:
             raise ValueError("ModifiedResNet needs an image size divisible by 32")
-        self.is3d = False
-        self.vis = None
+        # BatchNorm sums from its own pass instead of the producing GEMM's epilogue (diagnostics assign it) / the backward
+        # sums from the dX products
+        self.no_colstats, self.bn_bwd_fused = False, self.sw.bn_bwd_fused
         self.kq = 64 if _is16(dt) else 32             # GEMM K granularity (128 bytes)
         self.rnw: Dict[str, Tensor] = {}
         self.bns: List[_BN] = []
@@ -327,6 +330,7 @@ class RN50Engine(FairLoRAEngine):
         self.d_o, self.dqkv, self.dtok = e(T, E), e(T, 3 * E), [e(T, E), e(T, E)]
         self.dx4 = e(max_images * v.spacial * v.spacial, E)
         self.ev_ap = torch.cuda.Event()
+        self.ev_layer = [torch.cuda.Event()]                      # the stem's end -> the gradient stream (_vision_backward)
         self.aux_stream = self._aux0 = torch.cuda.Stream(device=dev)      # the downsample branches (_Bneck.forward / backward)
         self.bn_part_d = torch.zeros(self.bn_scratch, device=dev, dtype=torch.float32)
         self.bn_k12_d = torch.zeros(2 * self.bn_cmax, device=dev, dtype=torch.float32)
@@ -345,9 +349,6 @@ class RN50Engine(FairLoRAEngine):
         self.sops = SOperands(self.params, [site.prefix for blk in self.blocks for site, _ in blk.loras()], self.cfg,
                               self.device)
         self.pack_plan = ops.PackPlan(self.pack_entries, self.dtype, self.device) if self.fused_rank else None
-
-    def _n_layer_events(self) -> int:
-        return 1
 
     def set_overlap(self, on: bool) -> None:
         super().set_overlap(on)
@@ -430,20 +431,6 @@ class RN50Engine(FairLoRAEngine):
     def buffer_state(self) -> Dict[str, Tensor]:
         return {k: v.clone() for k, v in self.buffer_views().items()}
 
-    # -------------------------------------------------------------- evaluation --
-    # The forward-only pass of the ViT engine (its depth-independent workspace, FFM_EPI_GELU_ONLY) has no RN50 counterpart
-    # yet: `infer` is forward() (eval-mode BatchNorm as there) and a session changes nothing, so that a trainer treats both
-    # engines alike.
-    def _init_infer(self) -> None:
-        self.infer_ws = None
-
-    def inference(self):
-        import contextlib
-        return contextlib.nullcontext(self)
-
-    def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
-        return self.forward(image, attr)
-
     # ----------------------------------------------------------------- inputs --
     def _check_batch(self, image: Tensor) -> Tuple[int, int]:
         v = self.cfg.vision
@@ -456,7 +443,7 @@ class RN50Engine(FairLoRAEngine):
             raise ValueError(f"{b} images exceed the engine's max_images={self.max_images}")
         return b, 1
 
-    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor]):
+    def _load_inputs(self, image: Tensor, attr: Optional[Tensor], label: Optional[Tensor]) -> Tuple[int, int]:
         cfg = self.cfg
         image = self._as_f32(image)
         b, S = self._check_batch(image)
@@ -581,7 +568,7 @@ class RN50Engine(FairLoRAEngine):
         return out
 
 
-def create_engine(cfg, state_dict, **kw) -> FairLoRAEngine:
+def create_engine(cfg, state_dict, **kw) -> ClipEngine:
     """The engine class for cfg's image tower (MODEL.BACKBONE.NAME: ViT-B/16 or RN50)."""
     cls = RN50Engine if hasattr(cfg.vision, "embed_dim") else FairLoRAEngine
     return cls(cfg, state_dict, **kw)

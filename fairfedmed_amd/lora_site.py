@@ -1,12 +1,15 @@
 """One (Fair)LoRA-wrapped linear of either image tower: everything the engines know about it, in one object."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import TYPE_CHECKING, Optional, Tuple
 
 import torch
 
 from . import _lib as L
 from . import ops
+
+if TYPE_CHECKING:
+    from .engine import ClipEngine
 
 Tensor = torch.Tensor
 
@@ -25,7 +28,7 @@ class LoraSite:
     forward product writes (the evaluation pass keeps one pair for all layers).  fwd / bwd are the adapted products of
     both towers: the rank operands above around the caller's GEMM and its epilogue keywords."""
 
-    def __init__(self, eng, prefix: str, K: int, N: int, max_rows: int, fair: bool = True, u: Optional[Tensor] = None,
+    def __init__(self, eng: "ClipEngine", prefix: str, K: int, N: int, max_rows: int, fair: bool = True, u: Optional[Tensor] = None,
                  wide: bool = False, ln: Optional[Tuple[Tensor, Tensor]] = None,
                  row1415: Optional[Tuple[Tensor, Tensor]] = None):
         self.eng, self.prefix, self.K, self.N, self.fair = eng, prefix, K, N, fair

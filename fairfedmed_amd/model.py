@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import ops
 from .config import ModelCfg
-from .engine import FairLoRAEngine
+from .engine import ClipEngine
 from .synth import buffer_keys, lora_s_init, manifest, trainable_keys
 
 Tensor = torch.Tensor
@@ -77,7 +77,7 @@ class CustomCLIP(nn.Module):
         max_images = 32 if max_images is None else max_images
         self.cfg = cfg
         from .engine_rn import create_engine
-        self.engine = create_engine(cfg, state_dict, dtype=dtype, max_images=max_images, device=device)
+        self.engine: ClipEngine = create_engine(cfg, state_dict, dtype=dtype, max_images=max_images, device=device)
         train = set(trainable_keys(cfg))
         dev = self.engine.device
         # RN50: BatchNorm running statistics are buffers that training changes; they alias the engine's tensors
@@ -103,7 +103,7 @@ class CustomCLIP(nn.Module):
 
     def infer(self, image: Tensor, attr: Optional[Tensor] = None) -> Tensor:
         """forward()'s logits by the engine's forward-only evaluation pass (FairLoRAEngine.infer): bit-identical, nothing
-        kept for a backward pass, up to the engine's max_infer_images."""
+        kept for a backward pass, up to the engine's max_infer_images.  A tower without one runs forward() (ClipEngine.infer)."""
         return self.engine.infer(image, attr)
 
     def inference(self):
