@@ -22,6 +22,7 @@ EPI_ROWSTATS, EPI_LNIN, EPI_LGRAD, EPI_BNBWD = 128, 256, 512, 1024
 EPI_LNB_STAT, EPI_LNB_APPLY = 2048, 4096
 EPI_GELU_ONLY = 8192       # with EPI_GELU: `c` receives the activation, nothing else is stored (the evaluation pass)
 ABI_VERSION = 14
+FILTERS = {"bilinear": 0, "bicubic": 1}      # FFM_FILTER_*
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -112,6 +113,9 @@ SIGNATURES = {
     "ffm_ot_head_bwd": [_vp] * 8 + [_i32] * 6 + [_vp],
     "ffm_expand_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "ffm_resize_u8": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "ffm_augment_taps": [_i32, _i32, _i32],
+    "ffm_augment_boxes": [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
+    "ffm_crop_resize_u8": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_scale_check": [_vp, _f32, _i64, _vp, _vp],
     "ffm_attention_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],

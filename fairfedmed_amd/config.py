@@ -124,6 +124,55 @@ class OptimCfg:
     gamma: float = 0.1
 
 
+RANDOM_TRANSFORMS = ("random_resized_crop", "random_flip")
+INTERPOLATIONS = ("bilinear", "bicubic")
+
+
+@dataclass(frozen=True)
+class AugmentCfg:
+    """Train-time augmentation on the GPU: torchvision's RandomResizedCrop(scale, ratio) and
+    RandomHorizontalFlip with Pillow's antialiased `filter`, drawn per (seed, epoch, sample id)."""
+    crop: bool = False
+    flip: bool = False
+    scale: Tuple[float, float] = (0.08, 1.0)      # INPUT.RRCROP_SCALE
+    ratio: Tuple[float, float] = (3.0 / 4.0, 4.0 / 3.0)
+    filter: str = "bilinear"                      # INPUT.INTERPOLATION
+
+    def __post_init__(self):
+        if self.filter not in INTERPOLATIONS:
+            raise NotImplementedError(f"INPUT.INTERPOLATION {self.filter!r}: choose one of {INTERPOLATIONS}")
+        (s0, s1), (r0, r1) = self.scale, self.ratio
+        if not (0.0 < s0 <= s1 <= 1.0):
+            raise ValueError(f"INPUT.RRCROP_SCALE must satisfy 0 < lo <= hi <= 1, got {tuple(self.scale)}")
+        if not (0.0 < r0 <= r1 < float("inf")):
+            raise ValueError(f"the crop's aspect range must satisfy 0 < lo <= hi, got {tuple(self.ratio)}")
+
+    @property
+    def active(self) -> bool:
+        return self.crop or self.flip
+
+
+def augment_from_cfg(cfg):
+    """INPUT.TRANSFORMS / INPUT.RRCROP_SCALE / INPUT.INTERPOLATION of a config tree -> AugmentCfg, or None when no random
+    transform is configured.  'normalize' is accepted and changes nothing (the towers normalise); any other choice raises
+    NotImplementedError naming it; random transforms together with INPUT.NO_TRANSFORM raise ValueError."""
+    inp = getattr(cfg, "INPUT", None)
+    names = list(getattr(inp, "TRANSFORMS", None) or ())
+    for n in names:
+        if n not in RANDOM_TRANSFORMS + ("normalize",):
+            raise NotImplementedError(f"INPUT.TRANSFORMS: {n!r} is not built (choose from {RANDOM_TRANSFORMS + ('normalize',)})")
+    crop, flip = "random_resized_crop" in names, "random_flip" in names
+    if not (crop or flip):
+        return None
+    if getattr(inp, "NO_TRANSFORM", False):
+        raise ValueError(f"INPUT.TRANSFORMS {names} together with INPUT.NO_TRANSFORM: drop --input_no_transform or the random "
+                         "transforms (--transforms normalize)")
+    scale = tuple(float(v) for v in getattr(inp, "RRCROP_SCALE", (0.08, 1.0)))
+    if len(scale) != 2:
+        raise ValueError(f"INPUT.RRCROP_SCALE takes two values (lo, hi), got {scale}")
+    return AugmentCfg(crop=crop, flip=flip, scale=scale, filter=str(getattr(inp, "INTERPOLATION", "bilinear")))
+
+
 @dataclass(frozen=True)
 class ModelCfg:
     vision: Union[VisionCfg, ResNetCfg] = field(default_factory=VisionCfg)

@@ -131,14 +131,21 @@ class NativeBatch:
         C1, rep, R, T                 planes per image, channel repeat, output size, taps
         sizes                         ((H_b, W_b), ...) on the host (checks without a device read)"""
 
-    def __init__(self, pix, geom, start, w, C1: int, rep: int, R: int, sizes):
+    def __init__(self, pix, geom, start, w, C1: int, rep: int, R: int, sizes, ids=None, epoch: int = 0, seed: int = 0,
+                 augment=None):
         self.pix, self.geom, self.start, self.w = pix, geom, start, w
-        self.C1, self.rep, self.R, self.T, self.sizes = int(C1), int(rep), int(R), int(w.shape[-1]), tuple(sizes)
+        self.C1, self.rep, self.R, self.sizes = int(C1), int(rep), int(R), tuple(sizes)
+        self.T = 0 if w is None else int(w.shape[-1])
+        # train-time augmentation (section 4.20): the samples' dataset indices (int32 [B]), the loader's pass count and seed
+        # and the config.AugmentCfg; such a batch carries no tap tables (start and w are None) and is resampled by
+        # ops.augment_u8, every sample from a box of its own
+        self.ids, self.epoch, self.seed, self.augment = ids, int(epoch), int(seed), augment
 
     @classmethod
-    def from_planes(cls, samples: Sequence[np.ndarray], rep: int, R: int) -> "NativeBatch":
+    def from_planes(cls, samples: Sequence[np.ndarray], rep: int, R: int, tables: bool = True) -> "NativeBatch":
         """samples: uint8 arrays [C1, H_b, W_b].  A sample with H_b == R is one the readers do not resize (the decision is
-        the readers' own, by height alone), so its width must be R as well: the ValueError an engine gives such a batch."""
+        the readers' own, by height alone), so its width must be R as well: the ValueError an engine gives such a batch.
+        tables=False: bytes and geometry alone (the form `augmented` takes; table id -1)."""
         C1 = samples[0].shape[0]
         ids: Dict[tuple, int] = {}
         geom, off = [], 0
@@ -146,12 +153,16 @@ class NativeBatch:
             if s.dtype != np.uint8 or s.ndim != 3 or s.shape[0] != C1:
                 raise TypeError("NativeBatch takes uint8 samples [C1, H, W] with one C1")
             h, wd = s.shape[1:]
-            if h == R and wd != R:
+            if tables and h == R and wd != R:
                 raise ValueError(f"expected [B,{C1 * rep},{R},{R}], got {(1, C1 * rep, h, wd)}")
-            geom.append([off, h, wd, ids.setdefault((h, wd), len(ids))])
+            geom.append([off, h, wd, ids.setdefault((h, wd), len(ids)) if tables else -1])
             off += s.size
         if off >= 2 ** 31:
             raise ValueError("a NativeBatch holds less than 2 GiB of pixels")
+        if not tables:
+            pix = np.concatenate([np.ascontiguousarray(s).reshape(-1) for s in samples])
+            return cls(torch.from_numpy(pix), torch.tensor(geom, dtype=torch.int32), None, None, C1, rep, R,
+                       [(g[1], g[2]) for g in geom])
         taps = [(resize_taps(h, R), resize_taps(wd, R)) for h, wd in ids]
         T = max(t[1].shape[1] for pair in taps for t in pair)
         start = np.zeros((len(taps), 2, R), np.int32)
@@ -175,8 +186,25 @@ class NativeBatch:
     def is_cuda(self):
         return self.pix.is_cuda
 
+    @classmethod
+    def augmented(cls, samples: Sequence[np.ndarray], rep: int, R: int, ids, epoch: int, seed: int, augment) -> "NativeBatch":
+        """The batch a training loader with augmentation ships: stored bytes, geometry, and what keys the draws."""
+        nb = cls.from_planes(samples, rep, R, tables=False)
+        if len(ids) != len(samples):
+            raise ValueError("one dataset index per sample")
+        nb.ids = torch.as_tensor(np.asarray(ids, dtype=np.int64).astype(np.int32))
+        nb.epoch, nb.seed, nb.augment = int(epoch), int(seed), augment
+        return nb
+
+    @property
+    def max_extent(self) -> int:
+        """The largest stored height or width of the batch: what sizes ffm_crop_resize_u8's tap tables."""
+        return max(max(h, w) for h, w in self.sizes)
+
     def _map(self, fn) -> "NativeBatch":
-        return NativeBatch(fn(self.pix), fn(self.geom), fn(self.start), fn(self.w), self.C1, self.rep, self.R, self.sizes)
+        opt = lambda t: None if t is None else fn(t)
+        return NativeBatch(fn(self.pix), fn(self.geom), opt(self.start), opt(self.w), self.C1, self.rep, self.R, self.sizes,
+                           opt(self.ids), self.epoch, self.seed, self.augment)
 
     def to(self, device, non_blocking: bool = False) -> "NativeBatch":
         return self._map(lambda t: t.to(device, non_blocking=non_blocking))
@@ -187,6 +215,19 @@ class NativeBatch:
     def supported(self) -> bool:
         """Whether ffm_resize_u8 serves this batch (else it answers FFM_EUNSUP and the loader resizes on the host)."""
         return self.R % 4 == 0 and self.T <= NATIVE_MAX_TAPS
+
+
+def augment_refusal(augment, R: int, sizes) -> Optional[str]:
+    """Why ffm_crop_resize_u8 does not serve these stored sizes at output size R under `augment`, or None when it does."""
+    from . import _lib
+    if R % 4:
+        return f"INPUT.SIZE {R} is not a multiple of 4 (the kernel stores 16 bytes at a time): change INPUT.SIZE"
+    n = max(max(h, w) for h, w in sizes)
+    if _lib.load().ffm_augment_taps(int(n), int(R), _lib.FILTERS[augment.filter]) < 0:
+        return (f"a stored extent of {n} pixels resampled to INPUT.SIZE {R} with INPUT.INTERPOLATION {augment.filter} needs more "
+                f"filter taps than the kernel tabulates: store smaller images, raise INPUT.SIZE"
+                + (" or set INPUT.INTERPOLATION bilinear" if augment.filter != "bilinear" else ""))
+    return None
 
 
 def _read_csv(path: str) -> Dict[str, list]:
@@ -326,12 +367,29 @@ class FedLoader:
     stored uint8 samples at their stored sizes as a ``NativeBatch`` (``img`` has len() = B and .to() / .pin_memory(), no
     shape) and the engine resizes them on the GPU - a batch with a sample that is not uint8, or one ffm_resize_u8 does not
     serve, is resized on the host and shipped as float32; the 3D volumes are never resized and go as uint8.  Batches are
-    assembled in pinned memory so that the trainer's ``.to(device, non_blocking=True)`` is an asynchronous copy."""
+    assembled in pinned memory so that the trainer's ``.to(device, non_blocking=True)`` is an asynchronous copy.
+
+    augment=config.AugmentCfg (INPUT.TRANSFORMS; training loaders only, transport "native"): every batch is a ``NativeBatch`` that
+    carries ``ids`` (the dataset indices of its samples), ``epoch`` (the passes this loader has completed) and ``seed`` (this
+    loader's) and no tap tables, and the engine crops, resamples and flips it on the GPU.  What
+    cannot be augmented raises here, naming the setting to change; nothing is shipped un-augmented."""
 
     def __init__(self, dataset, batch_size: int, train: bool, seed: int = 0, transport: str = "float32",
-                 pin_memory: Optional[bool] = None):
+                 pin_memory: Optional[bool] = None, augment=None):
         assert transport in ("float32", "uint8", "native")
         self.dataset, self.batch_size, self.train, self.transport = dataset, batch_size, train, transport
+        # augment (config.AugmentCfg): training loaders only - a test loader never augments.  Its batches are NativeBatches
+        # that carry ids / epoch / seed and no tap tables; what cannot be augmented is refused, never shipped un-augmented
+        self.augment = augment if (train and augment is not None and augment.active) else None
+        self.seed, self.epoch = int(seed), 0                          # epoch: passes completed (settable)
+        if self.augment is not None:
+            if transport != "native":
+                raise ValueError(f"INPUT.TRANSFORMS run on the stored bytes: set --transport native (got {transport!r})")
+            if getattr(dataset, "modality_type", None) == "oct_bscans_3d":
+                raise ValueError("INPUT.TRANSFORMS: DATASET.MODALITY_TYPE oct_bscans_3d volumes are not augmented; choose "
+                                 "another modality or drop the random transforms (--transforms normalize)")
+            if dataset.resolution % 4:
+                raise ValueError(augment_refusal(self.augment, dataset.resolution, [(1, 1)]))
         self.drop_last = train and len(dataset) >= batch_size
         self.gen = np.random.default_rng(seed)
         self.pin = torch.cuda.is_available() if pin_memory is None else pin_memory
@@ -345,7 +403,16 @@ class FedLoader:
         native = self.transport == "native" and getattr(self.dataset, "modality_type", None) != "oct_bscans_3d"
         samples = [self.dataset.raw(int(i), native=True) if native else self.dataset.raw(int(i)) for i in idx]
         img = None
-        if native and all(s[0].dtype == np.uint8 for s in samples):
+        if self.augment is not None:
+            if not all(s[0].dtype == np.uint8 for s in samples):
+                raise TypeError("INPUT.TRANSFORMS: a stored sample is not uint8 and cannot be augmented on the GPU; store uint8 "
+                                "samples or drop the random transforms (--transforms normalize)")
+            why = augment_refusal(self.augment, self.dataset.resolution, [s[0].shape[1:] for s in samples])
+            if why:
+                raise ValueError("INPUT.TRANSFORMS: " + why)
+            img = NativeBatch.augmented([s[0] for s in samples], samples[0][1], self.dataset.resolution, idx, self.epoch,
+                                        self.seed, self.augment)
+        elif native and all(s[0].dtype == np.uint8 for s in samples):
             nb = NativeBatch.from_planes([s[0] for s in samples], samples[0][1], self.dataset.resolution)
             img = nb if nb.supported() else None
         if native and img is None:                                     # this batch takes the host resize
@@ -370,12 +437,15 @@ class FedLoader:
         order = self.gen.permutation(n) if self.train else np.arange(n)
         for b in range(len(self)):
             yield self._collate(order[b * self.batch_size:(b + 1) * self.batch_size])
+        self.epoch += 1
 
 
 class FedData:
     """What ``GLP_OT_SVLoRA(cfg, data=...)`` needs from the reference's DataManager: per-client loaders, class names."""
 
     def __init__(self, cfg, transport: str = "float32"):
+        from .config import augment_from_cfg
+        augment = augment_from_cfg(cfg)               # INPUT.TRANSFORMS: the training loaders augment, the test loaders never
         name = cfg.DATASET.NAME
         if name not in DATASET_DIRS:
             raise NotImplementedError(name)
@@ -389,7 +459,8 @@ class FedData:
             tr = cls(root, net_id + 1, train=True, **kw)
             te = cls(root, net_id + 1, train=False, **kw)
             self.fed_train_loader_x_dict[net_id] = FedLoader(tr, cfg.DATALOADER.TRAIN_X.BATCH_SIZE, True,
-                                                             seed=seed * 1000 + net_id, transport=transport)
+                                                             seed=seed * 1000 + net_id, transport=transport,
+                                                             augment=augment)
             self.fed_test_loader_x_dict[net_id] = FedLoader(te, cfg.TEST.BATCH_SIZE, False, transport=transport)
         self.classnames = list(CLASSNAMES[name])
         self.dataset = NS(classnames=self.classnames)

@@ -1080,7 +1080,8 @@ class ClipEngine:
     def _as_f32(self, image: Tensor, slot: str = "_u8_stage") -> Tensor:
         """uint8 transport (fairfedmed_amd.data, transport="uint8"): expand on the GPU to the float32 batch the
         reference's loader ships - a single SLO / X-ray channel is repeated to 3 (utils/data_utils.py:676-679).  A
-        NativeBatch (transport="native") carries stored sizes and its own channel repeat: resized into the same buffer."""
+        NativeBatch (transport="native") carries stored sizes and its own channel repeat: resized into the same buffer, or -
+        one that carries augmentation - cropped, resampled and flipped into it (ops.augment_u8)."""
         native = isinstance(image, NativeBatch)       # transport="native": stored sizes, resized here (ffm_resize_u8)
         if not native and image.dtype != torch.uint8:
             return image
@@ -1100,6 +1101,11 @@ class ClipEngine:
         if stage is None or stage.shape[0] < b or tuple(stage.shape[1:]) != shape[1:]:
             stage = torch.empty(shape, device=self.device, dtype=torch.float32)
             setattr(self, slot, stage)
+        if native and image.augment is not None:      # a training batch with INPUT.TRANSFORMS: every sample from its own box
+            boxes = getattr(self, "_aug_boxes", None)
+            if boxes is None or boxes.shape[0] < b:
+                boxes = self._aug_boxes = torch.empty(b, 8, device=self.device, dtype=torch.int32)
+            return ops.augment_u8(image, stage[:b], boxes[:b])
         if native:
             return ops.resize_u8(image, stage[:b])
         return ops.expand_u8(image.contiguous(), stage[:b], rep)

@@ -100,6 +100,13 @@ def build_parser() -> argparse.ArgumentParser:
     a("--synthetic", action="store_true", help="synthetic batches instead of the dataset under --root")
     a("--synthetic-batches", type=int, default=4)
     a("--transport", type=str, default="uint8", choices=["uint8", "float32", "native"])
+    a("--transforms", type=str, nargs="+", default=None,
+      help="INPUT.TRANSFORMS (the reference's flag): random_resized_crop and / or random_flip augment the training batches on "
+           "the GPU (needs --transport native); normalize is accepted and changes nothing (the towers normalise)")
+    a("--rrcrop_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+      help="INPUT.RRCROP_SCALE: the share of the stored area a random crop takes (default 0.08 1.0)")
+    a("--interpolation", type=str, default=None, choices=list(C.INTERPOLATIONS),
+      help="INPUT.INTERPOLATION: the filter of the crop's antialiased resample (default bilinear)")
     a("--input_size", type=int, default=0, help="INPUT.SIZE = (N, N); 0 keeps the configuration's (224)")
     a("--interpolate_pos", action="store_true",
       help="INPUT.INTERPOLATE_POS: run a ViT at an INPUT.SIZE other than its checkpoint's (a multiple of the patch size) with "
@@ -146,7 +153,8 @@ def setup_cfg(args) -> NS:
     cfg = NS(
         SEED=args.seed, OUTPUT_DIR=args.output_dir, VERBOSE=True,
         INPUT=NS(SIZE=(224, 224), PIXEL_MEAN=list(C.CLIP_PIXEL_MEAN), PIXEL_STD=list(C.CLIP_PIXEL_STD),
-                 NO_TRANSFORM=args.input_no_transform, INTERPOLATE_POS=args.interpolate_pos),
+                 NO_TRANSFORM=args.input_no_transform, INTERPOLATE_POS=args.interpolate_pos,
+                 TRANSFORMS=(), RRCROP_SCALE=(0.08, 1.0), INTERPOLATION="bilinear"),
         DATASET=NS(NAME="FairFedMed", ROOT=args.root, USERS=args.num_users, ATTRIBUTE_TYPE=args.attribute_type,
                    ATTRIBUTES=list(args.attributes), MODALITY_TYPE=args.modality_type,
                    DIM_PER_3D_SLICE=args.dim_per_3d_slice),
@@ -182,6 +190,12 @@ def setup_cfg(args) -> NS:
     if args.input_size:
         cfg.INPUT.SIZE = (args.input_size, args.input_size)
     cfg.INPUT.INTERPOLATE_POS = bool(args.interpolate_pos or getattr(cfg.INPUT, "INTERPOLATE_POS", False))
+    if args.transforms is not None:
+        cfg.INPUT.TRANSFORMS = tuple(args.transforms)
+    if args.rrcrop_scale is not None:
+        cfg.INPUT.RRCROP_SCALE = tuple(args.rrcrop_scale)
+    if args.interpolation is not None:
+        cfg.INPUT.INTERPOLATION = args.interpolation
     if args.backbone:
         cfg.MODEL.BACKBONE.NAME = args.backbone
     if args.trainer:
@@ -198,6 +212,13 @@ def check_scope(args, cfg) -> None:
         raise NotImplementedError(f"--OT {args.OT}: choose None (the FairLoRA scripts), Sinkhorn or COT")
     if not args.unfreeze_image_encoder:
         raise NotImplementedError("--unfreeze_image_encoder must be set: without it no FairLoRA adapter is injected")
+    aug = C.augment_from_cfg(cfg)                             # (an unknown transform, or one with INPUT.NO_TRANSFORM, raises)
+    if aug is not None and getattr(args, "synthetic", False):
+        raise ValueError(f"INPUT.TRANSFORMS {list(cfg.INPUT.TRANSFORMS)} with --synthetic: synthetic batches are float32 tensors "
+                         "with no stored bytes to crop; drop --synthetic or the random transforms")
+    if aug is not None and getattr(args, "transport", "native") != "native":
+        raise ValueError(f"INPUT.TRANSFORMS {list(cfg.INPUT.TRANSFORMS)} run on the stored bytes: set --transport native "
+                         f"(got {args.transport})")
 
 
 def fed_args(args):

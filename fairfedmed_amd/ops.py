@@ -574,6 +574,60 @@ def resize_u8(batch, dst: Tensor) -> Tensor:
     return dst
 
 
+def augment_taps(n: int, R: int, filter: str = "bilinear") -> int:
+    """Table width ffm_crop_resize_u8 needs for an axis of extent n resampled to R, or a negative code beyond
+    FFM_AUGMENT_MAX_TAPS / FFM_AUGMENT_MAX_LDS (ffm_augment_taps; needs no GPU)."""
+    return L.load().ffm_augment_taps(int(n), int(R), L.FILTERS[filter])
+
+
+def augment_boxes(geom: Tensor, ids: Tensor, seed: int, epoch: int, augment, boxes: Optional[Tensor] = None) -> Tensor:
+    """The crop box and flip of every sample of a ragged batch, drawn on the device (ffm_augment_boxes): boxes int32 [B, 8] =
+    {top, left, h, w, flip, attempt, 0, 0}.  geom: data.NativeBatch.geom; ids int32 [B]: the samples' dataset indices; augment:
+    config.AugmentCfg (crop, flip, scale, ratio).  The draws depend on (seed, epoch, id) and the stored size alone."""
+    _dev(geom, ids, boxes)
+    B = ids.numel()
+    if boxes is None:
+        boxes = torch.empty(B, 8, device=geom.device, dtype=torch.int32)
+    assert geom.dtype == torch.int32 and ids.dtype == torch.int32 and boxes.dtype == torch.int32
+    assert geom.is_contiguous() and ids.is_contiguous() and boxes.is_contiguous()
+    assert tuple(geom.shape) == (B, 4) and tuple(boxes.shape) == (B, 8)
+    rng = (C.c_double * 4)(augment.scale[0], augment.scale[1], augment.ratio[0], augment.ratio[1])
+    _call("ffm_augment_boxes", L.ptr(geom), L.ptr(ids), B, int(seed), int(epoch), int(bool(augment.crop)),
+          int(bool(augment.flip)), rng, L.ptr(boxes), L.stream_ptr())
+    return boxes
+
+
+def crop_resize_u8(batch, boxes: Tensor, dst: Tensor, filter: str = "bilinear", check_boxes: bool = True) -> Tensor:
+    """data.NativeBatch (stored uint8 samples, on the device) and one box per sample -> fp32 [B, C1*rep, R, R]: crop, Pillow's
+    antialiased resize, flip, float conversion and channel repeat in one launch (ffm_crop_resize_u8).  The kernel cannot
+    refuse a box it reads on the device (it leaves NaN for one outside its plane), so boxes a caller supplies are checked here
+    with a host read: check_boxes=False is for boxes ffm_augment_boxes has just written (ops.augment_u8: no host read)."""
+    _dev(batch.pix, batch.geom, boxes, dst)
+    B, R = len(batch), batch.R
+    assert batch.pix.dtype == torch.uint8 and batch.geom.dtype == torch.int32 and boxes.dtype == torch.int32
+    assert dst.dtype == torch.float32 and dst.is_contiguous()
+    assert all(t.is_contiguous() for t in (batch.pix, batch.geom, boxes))
+    assert tuple(batch.geom.shape) == (B, 4) and tuple(boxes.shape) == (B, 8) and tuple(dst.shape) == (B, batch.C1 * batch.rep, R, R)
+    assert len(batch.sizes) == B and sum(batch.C1 * h * w for h, w in batch.sizes) == batch.pix.numel()
+    if check_boxes:
+        for b, ((top, left, h, w), (H, W)) in enumerate(zip(boxes[:, :4].tolist(), batch.sizes)):
+            if not (0 <= top and 0 <= left and 0 < h <= H - top and 0 < w <= W - left):
+                raise RuntimeError(f"ffm_crop_resize_u8: box {(top, left, h, w)} of sample {b} lies outside its {H} x {W} plane "
+                                   "(unsupported size)")
+    _call("ffm_crop_resize_u8", L.ptr(batch.pix), L.ptr(batch.geom), L.ptr(boxes), L.ptr(dst), B, batch.C1, batch.rep, R,
+          L.FILTERS[filter], batch.max_extent, L.stream_ptr())
+    return dst
+
+
+def augment_u8(batch, dst: Tensor, boxes: Optional[Tensor] = None) -> Tensor:
+    """An augmenting data.NativeBatch (ids, epoch, seed, augment) -> fp32 [B, C1*rep, R, R]: the boxes, then the resample, both
+    on the current stream with no host read.  boxes: the caller's int32 [B, 8] buffer (the engine keeps one); None allocates."""
+    if batch.augment is None or batch.ids is None:
+        raise ValueError("augment_u8 takes a NativeBatch that carries ids, epoch, seed and an AugmentCfg")
+    boxes = augment_boxes(batch.geom, batch.ids, batch.seed, batch.epoch, batch.augment, boxes)
+    return crop_resize_u8(batch, boxes, dst, batch.augment.filter, check_boxes=False)
+
+
 EVAL_SLOTS = 10
 
 

@@ -163,6 +163,12 @@ class GLP_OT_SVLoRA:
             raise ValueError("no data: pass data=SyntheticFedData(...) (dataset I/O is out of scope)")
         self.fed_train_loader_x_dict = self.dm.fed_train_loader_x_dict
         self.fed_test_loader_x_dict = self.dm.fed_test_loader_x_dict
+        # INPUT.TRANSFORMS: the training loaders of data.FedData augment (section 4.20); a data manager whose loaders do not
+        # must not train silently un-augmented
+        aug = C.augment_from_cfg(cfg)
+        if aug is not None and any(getattr(l, "augment", None) != aug for l in self.fed_train_loader_x_dict.values()):
+            raise ValueError(f"INPUT.TRANSFORMS {list(cfg.INPUT.TRANSFORMS)}: the training loaders do not augment - build them "
+                             "with data.FedData(cfg, transport='native') (--transport native), or drop the random transforms")
         self.num_classes, self.lab2cname, self.classnames = self.dm.num_classes, self.dm.lab2cname, self.dm.classnames
         self._state_dict = state_dict if state_dict is not None else getattr(cfg.MODEL, "STATE_DICT", None)
         self.build_model()

@@ -55,7 +55,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_augment_boxes / ffm_crop_resize_u8 / ffm_augment_taps (train-time augmentation on the stored bytes, beside ffm_resize_u8, which is unchanged) are new symbols - purely additive; still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* The value in use for the diagnostic switch whose environment variable is `name` ("FFM_PANEL", "FFM_ATTN", ...: the rows
@@ -609,6 +609,51 @@ int ffm_expand_u8(const uint8_t* src, float* dst, int B, int C1, int HW, int rep
 #define FFM_RESIZE_MAX_TAPS 32
 int ffm_resize_u8(const uint8_t* pix, const int32_t* geom, const int32_t* tab_start, const float* tab_w, float* dst,
                   int B, int C1, int rep, int R, int T, void* stream);
+
+/*
+ * Train-time augmentation on the stored bytes (csrc/augment.hip; ABI 14, additive): torchvision's RandomResizedCrop and
+ * RandomHorizontalFlip on a PIL image - crop, then Pillow's antialiased resize - with counter-based draws keyed by the sample.
+ *
+ * ffm_augment_boxes: one thread per sample; boxes int32 [B][8] <- {top, left, h, w, flip, attempt, 0, 0} on the stored plane
+ * H x W of geom (ffm_resize_u8's; the offset and table id are not read).  ids int32 [B]: the samples' dataset indices.
+ *   x = Philox4x32-10(counter (ids[b], epoch, a, 0x4D475541), key (low, high word of seed)), u_j = ((x_j >> 9) + 0.5) 2^-23
+ *   attempts a = 0..9, in double: area = H W (s0 + u0 (s1 - s0)), asp = exp(ln r0 + u1 (ln r1 - ln r0)),
+ *     w = floor(sqrt(area asp) + 0.5), h = floor(sqrt(area / asp) + 0.5); accepted when 0 < w <= W and 0 < h <= H, with
+ *     top = min(floor(u2 (H - h + 1)), H - h) and left likewise from u3 and W - w;
+ *   after ten refusals the central box: W/H < r0: w = W, h = floor(w / r0 + 0.5); W/H > r1: h = H, w = floor(h r1 + 0.5);
+ *     else the whole plane; top = (H - h) / 2, left = (W - w) / 2 (integer division);
+ *   attempt = the accepted a, 10 for the central box, -1 with crop == 0 (the box is then the whole plane);
+ *   flip = (u0 of a = 10) < 0.5, and 0 with flip == 0.
+ * range: four doubles ON THE HOST, {s0, s1, r0, r1}, read before the call returns.  FFM_EINVAL: a NULL pointer, B <= 0,
+ * epoch < 0, a range outside 0 < s0 <= s1 <= 1 or 0 < r0 <= r1.
+ *
+ * ffm_crop_resize_u8: dst fp32 [B, C1*rep, R, R] (16-byte aligned) <- box b of every plane of image b, resampled to R x R;
+ * boxes as above (fields 0..4 are read; a caller may supply its own).  Per axis with n the box extent: scale = n / R,
+ * fs = max(1, scale), support = S fs (S = 1: FFM_FILTER_BILINEAR, the triangle; S = 2: FFM_FILTER_BICUBIC, Keys' cubic,
+ * a = -0.5); output o has centre c = (o + 0.5) scale and taps x in [max(0, int(c - support + 0.5)), min(n, int(c + support +
+ * 0.5))) with weight filter((x + 0.5 - c) / fs), normalised to sum 1 - in double, rounded once to fp32; taps stop at the box
+ * edges.  Sums in fp32 in a fixed order, one thread per output, no atomics: per source row the horizontal taps ascending, then
+ * the vertical taps ascending.  flip: output column c is column R - 1 - c of the unflipped result.  The result is clamped to
+ * [0, 255] and stored to each of the rep repeated channels; the C1 planes of an image share its box and flip.  A whole-plane
+ * box with H == W == R equals ffm_expand_u8 bit for bit.  One launch, no allocation, no host read: an image's bits depend on
+ * its own bytes and box alone.
+ * The tap tables are built per block in LDS, so an axis has at most FFM_AUGMENT_MAX_TAPS taps per output and the tables of a
+ * block at most FFM_AUGMENT_MAX_LDS bytes: ffm_augment_taps(n, R, filter) is the table width 2 ceil(support) + 1 an extent n
+ * needs (monotone in n), FFM_EUNSUP beyond either limit, FFM_EINVAL for n, R <= 0 or an unknown filter; it needs no GPU.
+ * max_extent: the largest H_b or W_b of the batch (a host value; the boxes live on the device): it sizes the tables.
+ * FFM_EUNSUP (nothing launched): R % 4 != 0, ffm_augment_taps(max_extent, R, filter) < 0, B * C1 > 2^27.  FFM_EINVAL: a NULL
+ * pointer, a size <= 0, an unknown filter, a misaligned geom / boxes / dst.  The call cannot read the boxes: a block whose
+ * box is not inside its plane, or needs wider tables than max_extent gave, reads no pixel and leaves NaN in its outputs.
+ */
+#define FFM_FILTER_BILINEAR 0
+#define FFM_FILTER_BICUBIC 1
+#define FFM_AUGMENT_MAX_TAPS 64
+#define FFM_AUGMENT_MAX_LDS 65536
+int ffm_augment_taps(int n, int R, int filter);
+int ffm_augment_boxes(const int32_t* geom, const int32_t* ids, int B, int64_t seed, int epoch, int crop, int flip,
+                      const double* range, int32_t* boxes, void* stream);
+int ffm_crop_resize_u8(const uint8_t* pix, const int32_t* geom, const int32_t* boxes, float* dst, int B, int C1, int rep,
+                       int R, int filter, int max_extent, void* stream);
 
 /*
  * Evaluator counts for binary tasks (evaluation/evaluator_oph.py:37-150; evaluation/metrics.py:197-311, 513-552;
