@@ -72,6 +72,7 @@ SIGNATURES = {
     "ffm_switch": [_vp, C.POINTER(_i32)],
     "ffm_gemm_nt": [C.POINTER(GemmArgs), _i32, _vp],
     "ffm_gemm_splitk_floats": [_i32, _i32, _i32, _i32],
+    "ffm_gemm_skinny": [_i32, _i32, _i32, _i32, _i32],
     "ffm_gemm_tiles_m": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "ffm_gemm_tiles_n": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "ffm_gemm_lgrad_rows": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
@@ -120,6 +121,7 @@ SIGNATURES = {
     "ffm_attention_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_attention_bwd_lnstat_ok": [_i32, _i32, _i32],
+    "ffm_attention_route": [_i32, _i32, _i32],
     "ffm_attention_bwd_lnstat": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ffm_lora_down": [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp,
                       _i32, _vp],

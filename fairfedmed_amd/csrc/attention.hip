@@ -1127,6 +1127,10 @@ static attn_gen attn_route(int L, int causal, int dtype) {
     return ATTN_NONE;
 }
 
+extern "C" int ffm_attention_route(int L, int causal, int dtype) {
+    return L > 0 ? (int)attn_route(L, causal, dtype) : 0;             // (the enum's values are the header's codes)
+}
+
 extern "C" int ffm_attention_fwd(const void* qkv, void* out, float* lse, int B, int L, int heads, int causal,
                                  int dtype, void* stream) {
     if (!qkv || !out || B <= 0 || L <= 0 || heads <= 0) return FFM_EINVAL;

@@ -986,10 +986,7 @@ extern "C" int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream) {
         if (((uintptr_t)a.bn_x | (uintptr_t)a.bn_mask | (uintptr_t)a.bn_gout) & 15) return FFM_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (ffm_skinny_ok(a, dtype) && !a.colstat_part) {                    // (column sums: the 128x128 kernel's epilogue)
-        const bool off = ffm_sw().skinny_off;                                // FFM_SKINNY=off: A/B runs
-        if (!off || dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) return ffm_skinny_launch(a, dtype, s);
-    }
+    if (ffm_skinny_ok(a, dtype)) return ffm_skinny_launch(a, dtype, s);   // (shape, epilogue, no column sums, FFM_SKINNY: gemm_skinny.hip)
     if (dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16) return FFM_EUNSUP;      // split-operand products: skinny shapes only
     if (a.flags & (FFM_EPI_LNB_STAT | FFM_EPI_LNB_APPLY)) {              // LayerNorm backward folded in: its arguments
         if ((a.flags & FFM_EPI_LNB_STAT) && !a.lnb_part) return FFM_EINVAL;

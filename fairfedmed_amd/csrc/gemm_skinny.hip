@@ -525,17 +525,28 @@ int launch_waves(const ffm_gemm_args& a, hipStream_t s) {
 
 }  // namespace
 
+// Does ffm_gemm_nt run this product here?  The ONE predicate: ffm_gemm_nt (csrc/gemm.hip) and the host query below both ask it.
+// Column sums (colstat_part) are an epilogue of the 128x128 kernel; FFM_SKINNY=off (A/B runs) leaves the split-operand
+// products, which no other kernel serves.
 bool ffm_skinny_ok(const ffm_gemm_args& a, int dtype) {
     if ((dtype != FFM_BF16 && dtype != FFM_F32 && dtype != FFM_F32_X3 && dtype != FFM_F32_X3_W16) || a.M > 16 * SK_MF || a.N % SK_COLS || a.K % 128)
         return false;
+    if (a.colstat_part) return false;
     switch (a.flags) {
         case 0:
         case FFM_EPI_BIAS:
         case FFM_EPI_BIAS | FFM_EPI_RESIDUAL:
         case FFM_EPI_BIAS | FFM_EPI_GELU:
-        case FFM_EPI_DGELU: return true;
+        case FFM_EPI_DGELU: return !ffm_sw().skinny_off || dtype == FFM_F32_X3 || dtype == FFM_F32_X3_W16;
     }
     return false;
+}
+
+// host query: that predicate for a product without colstat_part
+extern "C" int ffm_gemm_skinny(int M, int N, int K, int flags, int dtype) {
+    ffm_gemm_args a{};
+    a.M = M, a.N = N, a.K = K, a.flags = flags;
+    return ffm_skinny_ok(a, dtype) ? 1 : 0;
 }
 
 #ifndef FFM_TWIN_F16     // (defined once: the split products are float32-storage only, the half twin of this file has no use for it)

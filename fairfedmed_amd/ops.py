@@ -312,6 +312,12 @@ def gemm_splitk_floats(M: int, N: int, K: int, w16: bool = False) -> int:
     return int(L.load().ffm_gemm_splitk_floats(M, N, K, L.F32_X3_W16 if w16 else L.F32_X3))
 
 
+def gemm_skinny(M: int, N: int, K: int, flags: int = 0, dtype=torch.float32, x3: bool = False, w16: bool = False) -> bool:
+    """Whether gemm_nt (without colstats) runs this product on the skinny kernels (csrc/gemm_skinny.hip) - diagnostics."""
+    code = (L.F32_X3_W16 if w16 else L.F32_X3) if x3 else L.dtype_code(dtype)
+    return bool(L.load().ffm_gemm_skinny(M, N, K, flags, code))
+
+
 def layernorm_fwd(x: Tensor, y: Tensor, gamma: Tensor, beta: Tensor, mean: Optional[Tensor] = None,
                   rstd: Optional[Tensor] = None) -> Tensor:
     _dev(x, y, gamma, beta, mean, rstd)
@@ -730,6 +736,14 @@ def attention_fwd(qkv: Tensor, out: Tensor, lse: Optional[Tensor], B: int, Ltok:
     _call("ffm_attention_fwd", L.ptr(qkv), L.ptr(out), L.ptr(_f32(lse)), B, Ltok, heads, int(causal),
                                        L.dtype_code(qkv.dtype), L.stream_ptr())
     return out
+
+
+ATTN_ROUTES = {0: None, 1: "attention", 2: "attention_half_heads", 3: "attention3", 4: "attention_long"}
+
+
+def attention_route(Ltok: int, causal: bool, dtype: torch.dtype) -> Optional[str]:
+    """Which kernels serve attention_fwd / attention_bwd for this shape (ffm_attention_route) - diagnostics."""
+    return ATTN_ROUTES[L.load().ffm_attention_route(Ltok, int(causal), L.dtype_code(dtype))]
 
 
 def attention_bwd_lnstat_ok(Ltok: int, causal: bool, dtype: torch.dtype) -> bool:

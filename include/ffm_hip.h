@@ -55,7 +55,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_augment_boxes / ffm_crop_resize_u8 / ffm_augment_taps (train-time augmentation on the stored bytes, beside ffm_resize_u8, which is unchanged) are new symbols - purely additive; still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_gemm_skinny / ffm_attention_route (host queries beside ffm_gemm_tile_shape: does the skinny kernel serve this product, which attention kernels serve this length) are new symbols - purely additive; still 14: ffm_augment_boxes / ffm_crop_resize_u8 / ffm_augment_taps (train-time augmentation on the stored bytes, beside ffm_resize_u8, which is unchanged) are new symbols - purely additive; still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* The value in use for the diagnostic switch whose environment variable is `name` ("FFM_PANEL", "FFM_ATTN", ...: the rows
@@ -226,6 +226,10 @@ typedef struct ffm_gemm_args {
 int ffm_gemm_nt(const ffm_gemm_args* args, int dtype, void* stream);
 /* floats ffm_gemm_args.sk_part needs for this product (0: the product is not split over K) */
 int64_t ffm_gemm_splitk_floats(int M, int N, int K, int dtype);
+/* 1 when ffm_gemm_nt runs this product (without colstat_part) on the skinny kernels of csrc/gemm_skinny.hip (at most 64 rows,
+ * N % 16 == 0, K % 128 == 0, the plain / bias / bias + residual / bias + GELU / DGELU epilogues), 0 when it goes on to the
+ * 128 x 128 or the panel kernel.  Diagnostics, like ffm_gemm_tile_shape (which describes those two); needs no GPU. */
+int ffm_gemm_skinny(int M, int N, int K, int flags, int dtype);
 /* row tiles (= dS partial rows written under FFM_EPI_RANKOP) of the kernel ffm_gemm_nt picks for this call */
 int ffm_gemm_tiles_m(int M, int N, int K, int flags, int rank, int dtype, int packed);
 /* row tiles of lg_part_c / lg_part_a under FFM_EPI_LGRAD for this call (flags with or without the bit), or FFM_EUNSUP when
@@ -436,6 +440,10 @@ int ffm_attention_bwd(const void* qkv, const void* out, const void* dout, const 
  * shape is served (1) or ffm_attention_bwd_lnstat returns FFM_EUNSUP (0).
  */
 int ffm_attention_bwd_lnstat_ok(int L, int causal, int dtype);
+/* Which kernels serve ffm_attention_fwd / ffm_attention_bwd for this shape (diagnostics; needs no GPU): 1 csrc/attention.hip,
+ * whole key range in LDS; 2 its half-head variant (bf16 / half, unmasked, 129..224 tokens, behind FFM_ATTN=v2); 3 csrc/attention3.hip
+ * (16-bit, unmasked, 65..256 tokens); 4 the streaming kernels of csrc/attention_long.hip (more than 256 tokens); 0: none. */
+int ffm_attention_route(int L, int causal, int dtype);
 int ffm_attention_bwd_lnstat(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                              const float* ln_wg, const float* ln_d, float* ln_part, int B, int L, int heads, int causal,
                              int dtype, void* stream);

@@ -10,6 +10,8 @@ import math
 import pytest
 import torch
 
+from tests.guarded import guard_fixture
+
 pytestmark = pytest.mark.gpu
 
 DT = [torch.float32, torch.bfloat16, torch.float16]
@@ -58,29 +60,33 @@ def ref_attention(qkv, B, L, heads, causal):
     return o, torch.logsumexp(s, -1)
 
 
-def nan_like(*shape, dt=torch.float32):
-    return torch.full(shape, float("nan"), device="cuda", dtype=dt)
+@pytest.fixture
+def guard():
+    """Every kernel output of this file: poisoned body between two guard bands (tests/guarded.py); unchecked at teardown = failure."""
+    yield from guard_fixture()
 
 
-def run(ops, qkv, dout, B, L, heads, causal, with_lse=True):
-    """forward + backward into NaN-filled outputs: (out, lse, dqkv)"""
+def run(ops, guard, qkv, dout, B, L, heads, causal, with_lse=True):
+    """forward + backward into poisoned, guarded outputs: (out, lse, dqkv); lse is None for a forward without it"""
     E = heads * 64
-    out = nan_like(B * L, E, dt=qkv.dtype)
-    lse = nan_like(B, heads, L)
-    ops.attention_fwd(qkv, out, lse if with_lse else None, B, L, heads, causal)
+    out = guard.out(B * L, E, dtype=qkv.dtype, name="out")
+    lse = guard.out(B, heads, L, name="lse") if with_lse else None
+    ops.attention_fwd(qkv, out, lse, B, L, heads, causal)
     if dout is None:
+        guard.check()
         return out, lse, None
-    dqkv = nan_like(B * L, 3 * E, dt=qkv.dtype)
-    delta = nan_like(B, heads, L)
+    dqkv = guard.out(B * L, 3 * E, dtype=qkv.dtype, name="dqkv")
+    delta = guard.scratch(B, heads, L, name="delta")                  # (scratch by the header: bands only)
     ops.attention_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, causal)
+    guard.check()
     return out, lse, dqkv
 
 
-def fwd_bwd_against_float64(ops, dt, B, L, heads, causal):
+def fwd_bwd_against_float64(ops, guard, dt, B, L, heads, causal):
     E = heads * 64
     qkv = rnd(B * L, 3 * E, dt=dt, seed=23 + L)
     dout = rnd(B * L, E, dt=dt, seed=24 + L)
-    out, lse, dqkv = run(ops, qkv, dout, B, L, heads, causal)
+    out, lse, dqkv = run(ops, guard, qkv, dout, B, L, heads, causal)
     qd = qkv.double().requires_grad_(True)
     ref, ref_lse = ref_attention(qd, B, L, heads, causal)
     ref.backward(dout.double())
@@ -94,33 +100,33 @@ def fwd_bwd_against_float64(ops, dt, B, L, heads, causal):
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("L", LENGTHS)
-def test_long_lengths(ops, dt, L):
-    fwd_bwd_against_float64(ops, dt, 2, L, 3, False)
+def test_long_lengths(ops, guard, dt, L):
+    fwd_bwd_against_float64(ops, guard, dt, 2, L, 3, False)
 
 
-def test_long_grid_not_a_power_of_two(ops):
-    fwd_bwd_against_float64(ops, torch.bfloat16, 3, 577, 5, False)
+def test_long_grid_not_a_power_of_two(ops, guard):
+    fwd_bwd_against_float64(ops, guard, torch.bfloat16, 3, 577, 5, False)
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("B,L,heads", [(1, 300, 2), (2, 513, 1)])
-def test_long_causal(ops, dt, B, L, heads):
-    fwd_bwd_against_float64(ops, dt, B, L, heads, True)
+def test_long_causal(ops, guard, dt, B, L, heads):
+    fwd_bwd_against_float64(ops, guard, dt, B, L, heads, True)
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
-def test_long_forward_without_lse_gives_the_same_bits(ops, dt, causal):
+def test_long_forward_without_lse_gives_the_same_bits(ops, guard, dt, causal):
     B, L, heads = 2, 321, 3
     qkv = rnd(B * L, 3 * heads * 64, dt=dt, seed=31)
-    a, _, _ = run(ops, qkv, None, B, L, heads, causal, with_lse=True)
-    b, _, _ = run(ops, qkv, None, B, L, heads, causal, with_lse=False)
+    a, _, _ = run(ops, guard, qkv, None, B, L, heads, causal, with_lse=True)
+    b, _, _ = run(ops, guard, qkv, None, B, L, heads, causal, with_lse=False)
     assert bool(torch.isfinite(a.float()).all())
     assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-def test_long_online_softmax_rows(ops, dt):
+def test_long_online_softmax_rows(ops, guard, dt):
     """Three rows through the three ways a running maximum can move over the ten key tiles of L = 577: raised by the very
     last tile (one rescale of everything before), set by the first tile (never rescaled), and raised by every tile.
     Per-row comparison so that one wrong row cannot hide."""
@@ -134,7 +140,7 @@ def test_long_online_softmax_rows(ops, dt):
     v[1, 3, 1, 2] = -3.0                                   # query 40 of head 2 peaks at key 3 (first tile)
     v[1, 7, 0, 0] = 0.5                                    # query 7 of head 0: score 0.04 j + noise of 0.25, 2.56 per tile
     v[1, :, 1, 0] += (0.01 * torch.arange(L, device="cuda"))[:, None].to(dt)
-    out, lse, _ = run(ops, qkv, None, B, L, heads, False)
+    out, lse, _ = run(ops, guard, qkv, None, B, L, heads, False)
     ref, ref_lse = ref_attention(qkv.double(), B, L, heads, False)
     err = (out.double() - ref).abs().reshape(B, L, heads, 64).amax(-1)
     print("out", float(err.max()) / float(ref.abs().max()), "lse", float((lse.double() - ref_lse).abs().max()) / float(ref_lse.abs().max()))
@@ -149,7 +155,7 @@ def test_long_online_softmax_rows(ops, dt):
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
 @pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
-def test_long_propagates_non_finite_inputs(ops, dt, bad):
+def test_long_propagates_non_finite_inputs(ops, guard, dt, bad):
     """The step's only divergence guard is the finite flag ce_loss raises from the logits: a NaN / Inf in q, k or v must
     come out of the attention output (and one in dO out of dq, dk, dv), not be folded away by a running maximum, a rescale
     or a mask select - and must stay inside its (batch, head) pair."""
@@ -161,7 +167,7 @@ def test_long_propagates_non_finite_inputs(ops, dt, bad):
         qkv = rnd(B * L, 3 * E, dt=dt, seed=250)
         col = {"q": 0, "k": E, "v": 2 * E}[which] + h * 64 + 7
         qkv[b * L + row, col] = bad
-        out, _, _ = run(ops, qkv, None, B, L, heads, False)
+        out, _, _ = run(ops, guard, qkv, None, B, L, heads, False)
         o = out[rows, h * 64:(h + 1) * 64].float()
         hit = ~torch.isfinite(o).all(dim=1)
         if which == "q":
@@ -179,7 +185,7 @@ def test_long_propagates_non_finite_inputs(ops, dt, bad):
     qkv = rnd(B * L, 3 * E, dt=dt, seed=251)
     dout = rnd(B * L, E, dt=dt, seed=252)
     dout[b * L + 11, h * 64 + 3] = bad
-    _, _, dqkv = run(ops, qkv, dout, B, L, heads, False)
+    _, _, dqkv = run(ops, guard, qkv, dout, B, L, heads, False)
     dq = dqkv[rows, h * 64:(h + 1) * 64].float()
     dk = dqkv[rows, E + h * 64:E + (h + 1) * 64].float()
     dv = dqkv[rows, 2 * E + h * 64:2 * E + (h + 1) * 64].float()
@@ -191,19 +197,19 @@ def test_long_propagates_non_finite_inputs(ops, dt, bad):
     assert bool(torch.isfinite(dqkv.float()).all()), "outside the pair"
 
 
-def test_long_bitwise_repeatable_and_independent_of_the_grid(ops):
+def test_long_bitwise_repeatable_and_independent_of_the_grid(ops, guard):
     """No atomics and no sum across workgroups: three runs give the same bits, and so does the same batch as the first
     half of a batch twice as large (twice the grid)."""
     dt, B, L, heads = torch.bfloat16, 4, 577, 6
     E = heads * 64
     qkv = rnd(B * L, 3 * E, dt=dt, seed=901)
     dout = rnd(B * L, E, dt=dt, seed=902)
-    first = run(ops, qkv, dout, B, L, heads, False)
+    first = run(ops, guard, qkv, dout, B, L, heads, False)
     assert all(bool(torch.isfinite(t.float()).all()) for t in first)
     for _ in range(2):
-        again = run(ops, qkv, dout, B, L, heads, False)
+        again = run(ops, guard, qkv, dout, B, L, heads, False)
         assert all(torch.equal(a, b) for a, b in zip(first, again))
-    twice = run(ops, qkv.repeat(2, 1), dout.repeat(2, 1), 2 * B, L, heads, False)
+    twice = run(ops, guard, qkv.repeat(2, 1), dout.repeat(2, 1), 2 * B, L, heads, False)
     assert torch.equal(twice[0][:B * L], first[0])
     assert torch.equal(twice[1][:B], first[1])
     assert torch.equal(twice[2][:B * L], first[2])

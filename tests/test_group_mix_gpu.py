@@ -23,6 +23,7 @@ Assertions per launch (float64 references from the kernel's own rounded inputs, 
 import pytest
 import torch
 
+from tests.guarded import guard_fixture
 from tests.test_kernels_gpu import (DT, H16, IDS, check, mix, panel_fairlora_case, panel_layernorm_backward_fold_case,
                                     panel_lgrad_case, rnd, tol)
 
@@ -30,7 +31,6 @@ pytestmark = pytest.mark.gpu
 
 RPS = 37                      # rows per sample
 SCALING, LAM = 0.25, 0.7
-NAN = float("nan")
 DS_BOUND = 5e-5
 
 
@@ -38,6 +38,12 @@ DS_BOUND = 5e-5
 def ops():
     from fairfedmed_amd import ops
     return ops
+
+
+@pytest.fixture
+def guard():
+    """Every kernel output of this file: poisoned body between two guard bands (tests/guarded.py); unchecked at teardown = failure."""
+    yield from guard_fixture()
 
 
 def attr_pattern(G, M, rps=RPS, kind="mixed"):
@@ -100,10 +106,10 @@ def same_bits(got, ref, what):
 
 
 # ------------------------------------------------------- lora_down (both kernels) ---
-def down_launch(ops, x, P, rk, S, attr, r, G, with_ds, t_fwd, rps=RPS):
+def down_launch(ops, guard, x, P, rk, S, attr, r, G, with_ds, t_fwd, rps=RPS):
     M, K = x.shape
-    t, ts = torch.full((M, r), NAN, device="cuda"), torch.full((M, r), NAN, device="cuda")
-    dsp = torch.full((ops.lora_down_blocks(M, K, r, x.dtype), G, r), NAN, device="cuda") if with_ds else None
+    t, ts = guard.out(M, r), guard.out(M, r)
+    dsp = guard.out(ops.lora_down_blocks(M, K, r, x.dtype), G, r) if with_ds else None
     ops.lora_down(x, P, rk, S, attr, r, G, rps, SCALING, LAM, t, ts, t_fwd if with_ds else None, dsp)
     return {"t": t, "ts": ts, "dsp": dsp}
 
@@ -120,7 +126,7 @@ def down_checks(got, ref_t, S, attr, G, t_fwd, what, rps=RPS):
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("rk", [False, True], ids=["P_Kr", "P_rK"])
 @pytest.mark.parametrize("K", [128, 768, 3072])            # 1, 2 and 4 K slices per block (down_kq), in f32 and 16-bit alike
-def test_valu_lora_down(ops, dt, rk, K):
+def test_valu_lora_down(ops, guard, dt, rk, K):
     """lora_down_kernel (group_mix_w): 300 rows stay below the matrix-core kernel's 1024; r = 32 takes the second rank
     pass (j0 = 16)."""
     M = 300
@@ -134,20 +140,21 @@ def test_valu_lora_down(ops, dt, rk, K):
             S = rnd(G, r, seed=27)
             what = f"VALU lora_down r={r} G={G}"
             attr = attr_pattern(G, M)
-            got = down_launch(ops, x, P, rk, S, attr, r, G, True, t_fwd)
+            got = down_launch(ops, guard, x, P, rk, S, attr, r, G, True, t_fwd)
             down_checks(got, ref_t, S, attr, G, t_fwd, what)
-            fwd = down_launch(ops, x, P, rk, S, attr, r, G, False, t_fwd)        # the forward call: no t_fwd / ds_part
+            fwd = down_launch(ops, guard, x, P, rk, S, attr, r, G, False, t_fwd)        # the forward call: no t_fwd / ds_part
             assert torch.equal(fwd["t"], got["t"]) and torch.equal(fwd["ts"], got["ts"]), what + ": forward call differs"
-            none = down_launch(ops, x, P, rk, S, None, r, G, True, t_fwd)
+            none = down_launch(ops, guard, x, P, rk, S, None, r, G, True, t_fwd)
             down_checks(none, ref_t, S, None, G, t_fwd, what + " attr=None")
             for v in (-1, G):
-                same_bits(down_launch(ops, x, P, rk, S, attr_const(v, M), r, G, True, t_fwd), none, f"{what} all {v}")
+                same_bits(down_launch(ops, guard, x, P, rk, S, attr_const(v, M), r, G, True, t_fwd), none, f"{what} all {v}")
+    guard.check()
 
 
 @pytest.mark.parametrize("r", [5, 16])
 @pytest.mark.parametrize("G", [3, 8])                      # G * r = 128 > 64: the second store loop of the dS partial
 @H16
-def test_mfma_lora_down(ops, r, G, h16):
+def test_mfma_lora_down(ops, guard, r, G, h16):
     """lora_down_mfma_kernel: 16-bit storage, [r, K] rows, >= 1024 rows (1030: a ragged last 16-row block)."""
     dt, M, K = h16, 1030, 512
     # by construction not the VALU kernel: one dS partial row per 16 rows is the matrix-core kernel's block count
@@ -158,26 +165,27 @@ def test_mfma_lora_down(ops, r, G, h16):
     ref_t = x.double() @ P.to(dt).double().t()
     what = f"MFMA lora_down r={r} G={G}"
     attr = attr_pattern(G, M)
-    got = down_launch(ops, x, P, True, S, attr, r, G, True, t_fwd)
+    got = down_launch(ops, guard, x, P, True, S, attr, r, G, True, t_fwd)
     down_checks(got, ref_t, S, attr, G, t_fwd, what)
-    fwd = down_launch(ops, x, P, True, S, attr, r, G, False, t_fwd)
+    fwd = down_launch(ops, guard, x, P, True, S, attr, r, G, False, t_fwd)
     assert torch.equal(fwd["t"], got["t"]) and torch.equal(fwd["ts"], got["ts"]), what + ": forward call differs"
-    none = down_launch(ops, x, P, True, S, None, r, G, True, t_fwd)
+    none = down_launch(ops, guard, x, P, True, S, None, r, G, True, t_fwd)
     down_checks(none, ref_t, S, None, G, t_fwd, what + " attr=None")
     for v in (-1, G):
-        same_bits(down_launch(ops, x, P, True, S, attr_const(v, M), r, G, True, t_fwd), none, f"{what} all {v}")
+        same_bits(down_launch(ops, guard, x, P, True, S, attr_const(v, M), r, G, True, t_fwd), none, f"{what} all {v}")
     # the VALU kernel on the first 1000 rows (27 whole samples and a part of the 28th: the same attribute prefix) agrees
-    valu = down_launch(ops, x[:1000], P, True, S, attr[:(1000 + RPS - 1) // RPS].contiguous(), r, G, False, None)
+    valu = down_launch(ops, guard, x[:1000], P, True, S, attr[:(1000 + RPS - 1) // RPS].contiguous(), r, G, False, None)
     check(got["t"][:1000], valu["t"].double(), 2e-5, what + ": t against the VALU kernel")
     check_ts_per_sample(got["ts"][:1000], valu["ts"].double(), attr, RPS, 2e-5, what + " against the VALU kernel")
+    guard.check()
 
 
 # ------------------------------------------------- 128 x 128 GEMM, FFM_EPI_RANKOP ---
-def rankop_launch(ops, a, b, bias, rk_op, S, lw, kr, attr, r, G, t_fwd, rps=RPS):
+def rankop_launch(ops, guard, a, b, bias, rk_op, S, lw, kr, attr, r, G, t_fwd, rps=RPS):
     M, N = a.shape[0], b.shape[0]
-    out = torch.full((M, N), NAN, device="cuda", dtype=a.dtype)
-    t, ts = torch.full((M, r), NAN, device="cuda"), torch.full((M, r), NAN, device="cuda")
-    dsp = torch.full((ops.gemm_tiles_m(M), G, r), NAN, device="cuda")
+    out = guard.out(M, N, dtype=a.dtype)
+    t, ts = guard.out(M, r), guard.out(M, r)
+    dsp = guard.out(ops.gemm_tiles_m(M), G, r)
     ro = ops.RankOp(rk_op, S, attr, rps, SCALING, LAM, t_out=t, ts_out=ts, t_fwd=t_fwd, ds_part=dsp)
     ops.gemm_nt(a, b, out, bias=bias, lw=lw, lw_is_kr=kr, rankop=ro)
     return {"t": t, "ts": ts, "out": out, "dsp": dsp}
@@ -186,7 +194,7 @@ def rankop_launch(ops, a, b, bias, rk_op, S, lw, kr, attr, r, G, t_fwd, rps=RPS)
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("kr", [False, True], ids=["lw_rN", "lw_Nr"])
 @pytest.mark.parametrize("r", [8, 12, 16])                 # a power of two and any other rank take different dS code
-def test_gemm128_rank_epilogue(ops, dt, kr, r):
+def test_gemm128_rank_epilogue(ops, guard, dt, kr, r):
     M, N, K = 300, 256, 256
     a, b = rnd(M, K, dt=dt, seed=50), rnd(N, K, dt=dt, scale=K ** -0.5, seed=51)
     bias, P = rnd(N, seed=52), rnd(K, r, scale=0.1, seed=53)
@@ -210,11 +218,12 @@ def test_gemm128_rank_epilogue(ops, dt, kr, r):
             check_ds_per_group(got["dsp"], ref_t, t_fwd, pi_rows, SCALING, DS_BOUND, what)
 
         attr = attr_pattern(G, M)
-        checks(rankop_launch(ops, a, b, bias, rk_op, S, lw, kr, attr, r, G, t_fwd), attr, what)
-        none = rankop_launch(ops, a, b, bias, rk_op, S, lw, kr, None, r, G, t_fwd)
+        checks(rankop_launch(ops, guard, a, b, bias, rk_op, S, lw, kr, attr, r, G, t_fwd), attr, what)
+        none = rankop_launch(ops, guard, a, b, bias, rk_op, S, lw, kr, None, r, G, t_fwd)
         checks(none, None, what + " attr=None")
         for v in (-1, G):
-            same_bits(rankop_launch(ops, a, b, bias, rk_op, S, lw, kr, attr_const(v, M), r, G, t_fwd), none, f"{what} all {v}")
+            same_bits(rankop_launch(ops, guard, a, b, bias, rk_op, S, lw, kr, attr_const(v, M), r, G, t_fwd), none, f"{what} all {v}")
+    guard.check()
 
 
 # ------------------------------------------------------- panel GEMM, rank stage ---
@@ -235,33 +244,35 @@ def panel_m(case):
 @pytest.mark.parametrize("case", ["fc_fwd", "proj_fwd", "proj_dx", "fc_dx", "proj_dx_deriv"])
 @pytest.mark.parametrize("r,G", PANEL_RG)
 @H16
-def test_panel_rank_stage(ops, case, r, G, h16):
+def test_panel_rank_stage(ops, guard, case, r, G, h16):
     M = panel_m(case)
     what = f"panel {case} r={r} G={G}"
-    res = panel_fairlora_case(ops, case, M, r, G, attr_pattern(G, M), RPS, h16, before_checks=strict_checks(what))
-    none = panel_fairlora_case(ops, case, M, r, G, None, RPS, h16, before_checks=strict_checks(what + " attr=None"))
+    res = panel_fairlora_case(ops, guard, case, M, r, G, attr_pattern(G, M), RPS, h16, before_checks=strict_checks(what))
+    none = panel_fairlora_case(ops, guard, case, M, r, G, None, RPS, h16, before_checks=strict_checks(what + " attr=None"))
     ref = {k: getattr(none, k) for k in ("t", "ts", "out", "act", "dsp")}
     for v in (-1, G):
-        got = panel_fairlora_case(ops, case, M, r, G, attr_const(v, M), RPS, h16)
+        got = panel_fairlora_case(ops, guard, case, M, r, G, attr_const(v, M), RPS, h16)
         same_bits({k: getattr(got, k) for k in ref}, ref, f"{what} all {v}")
+    guard.check()
 
 
 @pytest.mark.mask_tolerant
 @pytest.mark.parametrize("r,G", PANEL_RG)
 @H16
-def test_panel_rank_stage_lgrad(ops, r, G, h16):
+def test_panel_rank_stage_lgrad(ops, guard, r, G, h16):
     M = M_LGRAD
     import os
     if "FFM_PANEL_MASK" not in os.environ:       # (under a tile mask without the 208 x 384 LGRAD tile the helper skips, as its own test does)
         assert ops.gemm_lgrad_rows(M, 3072, 768, r, h16, True) > 0, "the default tile set serves FFM_EPI_LGRAD at this shape"
-    panel_lgrad_case(ops, M, r, G, attr_pattern(G, M), RPS, h16, before_checks=strict_checks(f"panel LGRAD r={r} G={G}"))
+    panel_lgrad_case(ops, guard, M, r, G, attr_pattern(G, M), RPS, h16, before_checks=strict_checks(f"panel LGRAD r={r} G={G}"))
 
 
 @pytest.mark.mask_tolerant
 @pytest.mark.parametrize("r,G", [(4, 3), (4, 8), (8, 3), (8, 8), (12, 3), (12, 8)])     # (rows 14 / 15 of the rank operand are taken: r <= 14)
 @H16
-def test_panel_rank_stage_layernorm_fold(ops, r, G, h16):
+def test_panel_rank_stage_layernorm_fold(ops, guard, r, G, h16):
     """LNB_STAT (dX of c_proj, N = 3072) and LNB_APPLY (dX of c_fc, N = 768: the larger M of the two shapes)."""
     M = M_NARROW
-    panel_layernorm_backward_fold_case(ops, M, r, G, attr_pattern(G, M), RPS, h16,
+    panel_layernorm_backward_fold_case(ops, guard, M, r, G, attr_pattern(G, M), RPS, h16,
                                        before_checks=strict_checks(f"panel LayerNorm fold r={r} G={G}"))
+    guard.check()

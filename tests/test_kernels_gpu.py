@@ -11,6 +11,8 @@ import math
 import pytest
 import torch
 
+from tests.guarded import guard_fixture
+
 pytestmark = pytest.mark.gpu
 
 DT = [torch.float32, torch.bfloat16, torch.float16]
@@ -42,6 +44,12 @@ def ops():
     return ops
 
 
+@pytest.fixture
+def guard():
+    """Every kernel output of this file: poisoned body between two guard bands (tests/guarded.py); unchecked at teardown = failure."""
+    yield from guard_fixture()
+
+
 def rnd(*shape, dt=torch.float32, scale=1.0, seed=0):
     g = torch.Generator(device="cuda").manual_seed(seed + sum(shape))
     return (torch.randn(*shape, device="cuda", generator=g) * scale).to(dt)
@@ -50,27 +58,29 @@ def rnd(*shape, dt=torch.float32, scale=1.0, seed=0):
 # ------------------------------------------------------------------ GEMM ---
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("M,N,K", [(128, 128, 128), (200, 264, 192), (6304, 768, 768), (1000, 512, 3072)])
-def test_gemm_plain(ops, dt, M, N, K):
+def test_gemm_plain(ops, guard, dt, M, N, K):
     a, b = rnd(M, K, dt=dt, seed=1), rnd(N, K, dt=dt, scale=K ** -0.5, seed=2)
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
+    out = guard.out(M, N, dtype=dt)
     ops.gemm_nt(a, b, out)
     check(out, a.double() @ b.double().t(), tol(dt), "gemm")
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
-def test_gemm_asymmetric_identity(ops, dt):
+def test_gemm_asymmetric_identity(ops, guard, dt):
     # A = I, asymmetric B: catches a transposed C write or a wrong k mapping exactly
     n = 128
     a = torch.eye(n, device="cuda", dtype=dt)
     b = (torch.arange(n * n, device="cuda", dtype=torch.float32).reshape(n, n) % 251 - 125).to(dt)
-    out = torch.zeros(n, n, device="cuda", dtype=dt)
+    out = guard.out(n, n, dtype=dt)
     ops.gemm_nt(a, b, out)
     assert torch.equal(out.float(), b.float().t())
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("r,kr", [(4, False), (8, False), (8, True), (16, False), (32, True)])
-def test_gemm_fused_epilogue(ops, dt, r, kr):
+def test_gemm_fused_epilogue(ops, guard, dt, r, kr):
     M, N, K = 333, 384, 256
     a, b = rnd(M, K, dt=dt, seed=3), rnd(N, K, dt=dt, scale=K ** -0.5, seed=4)
     bias = rnd(N, seed=5)
@@ -79,14 +89,15 @@ def test_gemm_fused_epilogue(ops, dt, r, kr):
     res = rnd(M, N, dt=dt, seed=8)
     lwm = lw.t() if kr else lw
     ref = a.double() @ b.double().t() + bias.double() + ts.double() @ lwm.double() + res.double()
-    out = torch.empty(M, N, device="cuda", dtype=dt)
+    out = guard.out(M, N, dtype=dt)
     ops.gemm_nt(a, b, out, bias=bias, ts=ts, lw=lw, lw_is_kr=kr, res=res)
     check(out, ref, tol(dt), "gemm+bias+lora+res")
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("r,G,kr,use_attr", [(8, 3, False, True), (16, 3, True, True), (4, 2, False, False), (12, 3, True, True)])
-def test_gemm_rankop_fused_lora(ops, dt, r, G, kr, use_attr):
+def test_gemm_rankop_fused_lora(ops, guard, dt, r, G, kr, use_attr):
     """FFM_EPI_RANKOP: t = a . P (inside the GEMM), ts = scaling t s_b, out = a b^T + bias + ts lw, dS partials."""
     M, N, K, rps = 700, 384, 256, 197
     a, b = rnd(M, K, dt=dt, seed=50), rnd(N, K, dt=dt, scale=K ** -0.5, seed=51)
@@ -100,9 +111,9 @@ def test_gemm_rankop_fused_lora(ops, dt, r, G, kr, use_attr):
     rk = torch.zeros(16, K, device="cuda", dtype=dt)
     ops.PackPlan([(P, False, rk)], dt, "cuda").run()
     assert torch.equal(rk[:r].float(), P.t().to(dt).float()) and float(rk[r:].abs().sum()) == 0.0
-    out = torch.empty(M, N, device="cuda", dtype=dt)
-    t, ts = torch.empty(M, r, device="cuda"), torch.empty(M, r, device="cuda")
-    dsp = torch.full((ops.gemm_tiles_m(M), G, r), float("nan"), device="cuda")
+    out = guard.out(M, N, dtype=dt)
+    t, ts = guard.out(M, r), guard.out(M, r)
+    dsp = guard.out(ops.gemm_tiles_m(M), G, r)
     ro = ops.RankOp(rk, S, attr, rps, 0.25, 0.7, t_out=t, ts_out=ts, t_fwd=t_fwd, ds_part=dsp)
     ops.gemm_nt(a, b, out, bias=bias, lw=lw, lw_is_kr=kr, rankop=ro)
     ref_t = a.double() @ P.to(dt).double()
@@ -115,6 +126,7 @@ def test_gemm_rankop_fused_lora(ops, dt, r, G, kr, use_attr):
     check(ts, ref_ts, 2e-5, "ts")
     check(out, a.double() @ b.double().t() + bias.double() + ref_ts @ lwm, tol(dt), "fused out")
     check(dsp.double().sum(0), pi_rows.t() @ (0.25 * t_fwd.double() * ref_t), 5e-5, "dS")
+    guard.check()
 
 
 
@@ -123,7 +135,11 @@ def test_gemm_rankop_fused_lora(ops, dt, r, G, kr, use_attr):
 @pytest.mark.parametrize("M,N,K,mode", [(6304, 2048, 1536, "b"), (6304, 768, 768, "br"), (6304, 768, 2304, ""),
                                          (6000, 768, 3072, "br"), (4100, 1024, 512, "b")])
 @H16
-def test_gemm_panel_plain(ops, M, N, K, mode, h16):
+def test_gemm_panel_plain(ops, guard, M, N, K, mode, h16):
+    panel_plain_case(ops, guard, M, N, K, mode, h16)
+
+
+def panel_plain_case(ops, guard, M, N, K, mode, h16):
     """Frozen weights packed in MFMA-fragment order -> panel kernel (csrc/gemm_panel_impl.h); same contract as
     ffm_gemm_nt on the row-major operand."""
     dt = h16
@@ -139,27 +155,28 @@ def test_gemm_panel_plain(ops, M, N, K, mode, h16):
     if "r" in mode:
         kw["res"] = rnd(M, N, dt=dt, seed=63)
         ref = ref + kw["res"].double()
-    out = torch.empty(M, N, device="cuda", dtype=dt)
+    out = guard.out(M, N, dtype=dt)
     ops.gemm_nt(a, b, out, b_packed=ops.pack_b(b), **kw)
     check(out, ref, tol(dt), "panel " + mode)
-    out2 = torch.empty_like(out)
+    out2 = guard.like(out)
     ops.gemm_nt(a, b, out2, **kw)                    # the 128x128 kernel on the same operands
     check(out, out2.double(), 1e-2, "panel vs 128x128")
+    guard.check()
 
 
 @pytest.mark.mask_tolerant
 @pytest.mark.parametrize("case", ["fc_fwd", "proj_fwd", "proj_dx", "fc_dx", "proj_dx_deriv"])
 @pytest.mark.parametrize("M,r,G,use_attr", [(6304, 8, 3, True), (5500, 16, 2, False), (6304, 4, 3, True)])
 @H16
-def test_gemm_panel_fairlora(ops, case, M, r, G, use_attr, h16):
+def test_gemm_panel_fairlora(ops, guard, case, M, r, G, use_attr, h16):
     """The four FairLoRA GEMMs of a block on the panel kernel: t / ts / dS partials / fused rank-r update / GELU."""
     rps = 197
     nsamp = (M + rps - 1) // rps
     attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
-    panel_fairlora_case(ops, case, M, r, G, attr, rps, h16)
+    panel_fairlora_case(ops, guard, case, M, r, G, attr, rps, h16)
 
 
-def panel_fairlora_case(ops, case, M, r, G, attr, rps, dt, before_checks=None):
+def panel_fairlora_case(ops, guard, case, M, r, G, attr, rps, dt, before_checks=None, rowstats=False, shape=None):
     """Body of test_gemm_panel_fairlora for a given attribute vector ([ceil(M / rps)] int32 or None) and rows per sample.
     `before_checks(res)` (tests/test_group_mix_gpu.py) sees every tensor of the launch and its float64 reference before
     this function's own assertions run."""
@@ -167,6 +184,8 @@ def panel_fairlora_case(ops, case, M, r, G, attr, rps, dt, before_checks=None):
     deriv = case == "proj_dx_deriv"               # dX(c_proj) with the saved tensor = quick_gelu'(pre) (gelu_deriv)
     case = "proj_dx" if deriv else case
     N, K = (4 * width, width) if case in ("fc_fwd", "proj_dx") else (width, 4 * width)
+    if shape is not None:                         # (N, K) other than the ViT-B/16 block's (tests/test_guard_bands_gpu.py)
+        N, K = shape
     kr = case in ("proj_dx", "fc_dx")
     flags = {"fc_fwd": 1 | 2 | 16, "proj_fwd": 1 | 2 | 8, "proj_dx": 2 | 4 | 32, "fc_dx": 2 | 4}[case] | 64
     nrows = ops.gemm_tiles_m(M, N, K, flags, r, dt, True)
@@ -177,11 +196,11 @@ def panel_fairlora_case(ops, case, M, r, G, attr, rps, dt, before_checks=None):
     lw = rnd(N, r, seed=75) if kr else rnd(r, N, seed=75)
     rk = torch.zeros(16, K, device="cuda", dtype=dt)
     ops.PackPlan([(P, False, rk)], dt, "cuda").run()
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
-    t, ts = torch.full((M, r), float("nan"), device="cuda"), torch.full((M, r), float("nan"), device="cuda")
+    out = guard.out(M, N, dtype=dt)
+    t, ts = guard.out(M, r), guard.out(M, r)
     kw, bwd = {}, kr
     t_fwd = rnd(M, r, seed=76) if bwd else None
-    dsp = torch.full((nrows, G, r), float("nan"), device="cuda") if bwd else None
+    dsp = guard.out(nrows, G, r) if bwd else None
     ro = ops.RankOp(rk, S, attr, rps, 0.25, 0.7, t_out=t, ts_out=ts, t_fwd=t_fwd, ds_part=dsp)
     ref_t = a.double() @ P.to(dt).double()
     pi = mix(attr, G)
@@ -196,9 +215,16 @@ def panel_fairlora_case(ops, case, M, r, G, attr, rps, dt, before_checks=None):
     if case == "proj_fwd":
         kw["res"] = rnd(M, N, dt=dt, seed=77)
         ref = ref + kw["res"].double()
+    rs_part = None
+    if rowstats:                                     # FFM_EPI_ROWSTATS beside the c_proj forward: [tiles_n, M, 2], exactly
+        assert case == "proj_fwd"
+        tn = ops.gemm_tiles_n(M, N, K, flags | 128, r, dt, True)
+        assert tn > 0, "no FFM_EPI_ROWSTATS kernel for this shape"
+        rs_part = guard.out(tn, M, 2)
+        kw["rowstats"] = rs_part
     act = None
     if case == "fc_fwd":
-        act = torch.empty(M, N, device="cuda", dtype=dt)
+        act = guard.out(M, N, dtype=dt)
         kw["gelu_out"] = act
     if case == "proj_dx":
         kw["dgelu_aux"] = rnd(M, N, dt=dt, seed=78)
@@ -219,15 +245,20 @@ def panel_fairlora_case(ops, case, M, r, G, attr, rps, dt, before_checks=None):
     if act is not None:
         pre = out.double()
         check(act, pre * torch.sigmoid(1.702 * pre), tol(dt), "quick_gelu(pre)")
+    if rs_part is not None:                          # sums of the STORED rows, as test_gemm_rowstats_partials holds them
+        o, got = out.double(), rs_part.double().sum(0)
+        check(got[:, 0], o.sum(1), 1e-5, "row sums")
+        check(got[:, 1], (o * o).sum(1), 1e-5, "row sums of squares")
     if bwd:
         check(dsp.double().sum(0), pi_rows.t() @ (0.25 * t_fwd.double() * ref_t), 5e-5, "dS")
+    guard.check()
     return res
 
 
 @pytest.mark.mask_tolerant
 @pytest.mark.parametrize("M,r,G,use_attr", [(6304, 8, 3, True), (6250, 16, 2, False), (6304, 4, 3, True), (3000, 8, 3, True)])
 @H16
-def test_gemm_panel_lgrad_partials(ops, M, r, G, use_attr, h16):
+def test_gemm_panel_lgrad_partials(ops, guard, M, r, G, use_attr, h16):
     """FFM_EPI_LGRAD: the dX product of c_proj also leaves the per-row-tile partial products of the two large rank-r
     gradient reductions of the block - dB(c_fc) = dpre^T ts1 from the rows it stores and dA(c_proj) = act^T us from
     quick_gelu(pre) and its own ts.  Held to float64 on the 16-bit tensors the kernel itself produced, and to the
@@ -235,14 +266,14 @@ def test_gemm_panel_lgrad_partials(ops, M, r, G, use_attr, h16):
     rps = 197
     nsamp = (M + rps - 1) // rps
     attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
-    panel_lgrad_case(ops, M, r, G, attr, rps, h16)
+    panel_lgrad_case(ops, guard, M, r, G, attr, rps, h16)
 
 
-def panel_lgrad_case(ops, M, r, G, attr, rps, dt, before_checks=None):
+def panel_lgrad_case(ops, guard, M, r, G, attr, rps, dt, before_checks=None, shape=None):
     """Body of test_gemm_panel_lgrad_partials for a given attribute vector and rows per sample (`before_checks`: as in
     panel_fairlora_case, on the launch WITH the partial products)."""
     width = 768
-    N, K = 4 * width, width
+    N, K = shape if shape is not None else (4 * width, width)
     nlg = ops.gemm_lgrad_rows(M, N, K, r, dt, True)
     if nlg <= 0:
         pytest.skip("no FFM_EPI_LGRAD kernel for this shape (the engine then launches the reductions)")
@@ -258,15 +289,15 @@ def panel_lgrad_case(ops, M, r, G, attr, rps, dt, before_checks=None):
     bp = ops.pack_b(b)
 
     def run(lgrad):
-        out = torch.empty(M, N, device="cuda", dtype=dt)
-        t, ts = torch.full((M, r), float("nan"), device="cuda"), torch.full((M, r), float("nan"), device="cuda")
-        dsp = torch.full((nrows, G, r), float("nan"), device="cuda")
+        out = guard.out(M, N, dtype=dt)
+        t, ts = guard.out(M, r), guard.out(M, r)
+        dsp = guard.out(nrows, G, r)
         ro = ops.RankOp(rk, S, attr, rps, 0.25, 0.7, t_out=t, ts_out=ts, t_fwd=t_fwd, ds_part=dsp, lgrad=lgrad)
         ops.gemm_nt(a, b, out, lw=lw, lw_is_kr=True, rankop=ro, b_packed=bp, dgelu_aux=pre)
         return out, t, ts, dsp
 
-    pc = torch.full((nlg, N, r), float("nan"), device="cuda")
-    pa = torch.full((nlg, N, r), float("nan"), device="cuda")
+    pc = guard.out(nlg, N, r)
+    pa = guard.out(nlg, N, r)
     out, t, ts, dsp = run((ts1, pc, pa))
     out0, t0, ts0, dsp0 = run(None)
     if before_checks is not None:
@@ -287,14 +318,15 @@ def panel_lgrad_case(ops, M, r, G, attr, rps, dt, before_checks=None):
     # (quick_gelu by v_exp / v_rcp: a 16-bit rounding flips here and there against torch's sigmoid)
     check(pa.double().sum(0), ref_a, 2e-3, "dA(c_proj) partials")
     ns = ops.lora_grad_splits(M)
-    part = torch.empty(ns * N * r, device="cuda")
+    part = guard.out(ns * N * r)
     ops.lora_grad_partial(out, ts1, r, part)
     check(pc.double().sum(0), part.view(ns, N, r).double().sum(0), 2e-5, "against ffm_lora_grad_partial")
+    guard.check()
 
 
 @pytest.mark.mask_tolerant
 @H16
-def test_gemm_panel_lgrad_race_screen_bitwise_repeatable(ops, h16):
+def test_gemm_panel_lgrad_race_screen_bitwise_repeatable(ops, guard, h16):
     """The FFM_EPI_LGRAD epilogue lays two 16-bit images over the part of the wave's output stage it has already read and
     orders its LDS traffic by program order inside the wave (asm ds_write / ds_read_b64_tr_b16 between compiler-visible
     loads), its V tables by the block's barriers, its MFMA results by hand-placed wait states: a hazard there shows as a value
@@ -316,10 +348,10 @@ def test_gemm_panel_lgrad_race_screen_bitwise_repeatable(ops, h16):
     flush = torch.empty(320 << 20, device="cuda", dtype=torch.uint8)
     first = None
     for it in range(24):
-        out = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
-        t, ts = torch.full((M, r), float("nan"), device="cuda"), torch.full((M, r), float("nan"), device="cuda")
-        dsp = torch.full((nrows, G, r), float("nan"), device="cuda")
-        pc, pa = torch.full((nlg, N, r), float("nan"), device="cuda"), torch.full((nlg, N, r), float("nan"), device="cuda")
+        out = guard.out(M, N, dtype=dt)
+        t, ts = guard.out(M, r), guard.out(M, r)
+        dsp = guard.out(nrows, G, r)
+        pc, pa = guard.out(nlg, N, r), guard.out(nlg, N, r)
         if it % 3 == 1:
             flush.fill_(it)
         ro = ops.RankOp(rk, S, attr, rps, 0.25, 0.7, t_out=t, ts_out=ts, t_fwd=t_fwd, ds_part=dsp, lgrad=(ts1, pc, pa))
@@ -331,15 +363,16 @@ def test_gemm_panel_lgrad_race_screen_bitwise_repeatable(ops, h16):
         else:
             for x, y, nm in zip(cur, first, ("out", "t", "ts", "dS", "part_c", "part_a")):
                 assert torch.equal(x, y), f"run {it}: {nm} differs from run 0 in {int((x != y).sum())} elements"
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
-def test_gemm_gelu_and_dgelu(ops, dt):
+def test_gemm_gelu_and_dgelu(ops, guard, dt):
     M, N, K = 260, 256, 128
     a, b = rnd(M, K, dt=dt, seed=9), rnd(N, K, dt=dt, scale=K ** -0.5 * 2, seed=10)
     bias = rnd(N, seed=11)
-    pre = torch.empty(M, N, device="cuda", dtype=dt)
-    act = torch.empty(M, N, device="cuda", dtype=dt)
+    pre = guard.out(M, N, dtype=dt)
+    act = guard.out(M, N, dtype=dt)
     ops.gemm_nt(a, b, pre, bias=bias, gelu_out=act)
     ref_pre = a.double() @ b.double().t() + bias.double()
     check(pre, ref_pre, tol(dt), "pre")
@@ -347,22 +380,27 @@ def test_gemm_gelu_and_dgelu(ops, dt):
     check(act, p * torch.sigmoid(1.702 * p), tol(dt), "quick_gelu(pre)")
     # dgelu: out = (a b^T) * gelu'(aux)
     aux = rnd(M, N, dt=dt, seed=12)
-    out = torch.empty(M, N, device="cuda", dtype=dt)
+    out = guard.out(M, N, dtype=dt)
     ops.gemm_nt(a, b, out, dgelu_aux=aux)
     x = aux.double()
     s = torch.sigmoid(1.702 * x)
     check(out, (a.double() @ b.double().t()) * (s * (1 + 1.702 * x * (1 - s))), tol(dt), "dgelu")
+    guard.check()
 
 
 # ------------------------------------------------------------- LayerNorm ---
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("rows,width", [(6304, 768), (308, 512), (37, 128), (5, 2048)])
-def test_layernorm_fwd_bwd(ops, dt, rows, width):
+def test_layernorm_fwd_bwd(ops, guard, dt, rows, width):
+    layernorm_case(ops, guard, dt, rows, width)
+
+
+def layernorm_case(ops, guard, dt, rows, width):
     x = rnd(rows, width, dt=dt, seed=13) * 2 + 0.5
     gamma, beta = 1 + 0.1 * rnd(width, seed=14), 0.1 * rnd(width, seed=15)
-    y = torch.empty_like(x)
-    mean = torch.empty(rows, device="cuda")
-    rstd = torch.empty(rows, device="cuda")
+    y = guard.like(x)
+    mean = guard.out(rows)
+    rstd = guard.out(rows)
     ops.layernorm_fwd(x, y, gamma, beta, mean, rstd)
     xd = x.double().requires_grad_(True)
     ref = torch.nn.functional.layer_norm(xd, (width,), gamma.double(), beta.double(), 1e-5)
@@ -371,39 +409,49 @@ def test_layernorm_fwd_bwd(ops, dt, rows, width):
     dy = rnd(rows, width, dt=dt, seed=16)
     res = rnd(rows, width, dt=dt, seed=17)
     ref.backward(dy.double())
-    out = torch.empty_like(x)
+    out = guard.like(x)
     ops.layernorm_bwd(dy, x, gamma, mean, rstd, res, out)
     check(out, xd.grad + res.double(), tol(dt), "ln bwd + res")
     ops.layernorm_bwd(dy, x, gamma, mean, rstd, None, out)
     check(out, xd.grad, tol(dt), "ln bwd")
+    guard.check()
 
 
 # ---------------------------------------------------- patchify / embed ----
 @pytest.mark.parametrize("dt", DT, ids=IDS)
-def test_patchify_and_embed(ops, dt):
-    B, H, ps, width = 3, 64, 16, 128
+def test_patchify_and_embed(ops, guard, dt):
+    patchify_and_embed_case(ops, guard, dt, 3)
+
+
+def patchify_and_embed_case(ops, guard, dt, B, rowsums=False):
+    H, ps, width = 64, 16, 128
     img = torch.rand(B, 3, H, H, device="cuda") * 255
     mean3, std3 = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
     P = (H // ps) ** 2
-    cols = torch.empty(B * P, 3 * ps * ps, device="cuda", dtype=dt)
+    cols = guard.out(B * P, 3 * ps * ps, dtype=dt)
     ops.patchify(img, cols, ps, mean3, std3)
     x = (img / 255.0 - torch.tensor(mean3, device="cuda").view(1, 3, 1, 1)) / torch.tensor(std3, device="cuda").view(1, 3, 1, 1)
     ref = torch.nn.functional.unfold(x, kernel_size=ps, stride=ps).transpose(1, 2).reshape(B * P, -1)
     check(cols, ref, 1e-6 if dt == torch.float32 else 8e-3, "patchify")
     # conv1 as a GEMM over the gathered patches == F.conv2d
     w = rnd(width, 3, ps, ps, scale=0.02, seed=18)
-    out = torch.empty(B * P, width, device="cuda", dtype=dt)
+    out = guard.out(B * P, width, dtype=dt)
     ops.gemm_nt(cols, w.reshape(width, -1).to(dt), out)
     conv = torch.nn.functional.conv2d(x.double(), w.to(dt).double(), stride=ps).reshape(B, width, P).permute(0, 2, 1)
     check(out, conv.reshape(B * P, width), tol(dt) * 2, "patch-embed")
     # token assembly + ln_pre
     cls, pos = rnd(width, dt=dt, scale=0.1, seed=19), rnd(P + 1, width, dt=dt, scale=0.1, seed=20)
     gamma, beta = 1 + 0.1 * rnd(width, seed=21), 0.1 * rnd(width, seed=22)
-    xt = torch.empty(B * (P + 1), width, device="cuda", dtype=dt)
-    ops.embed_lnpre(out, cls, pos, gamma, beta, xt, B, P + 1)
+    xt = guard.out(B * (P + 1), width, dtype=dt)
+    rs = guard.out(B * (P + 1), 2) if rowsums else None
+    ops.embed_lnpre(out, cls, pos, gamma, beta, xt, B, P + 1, rowstat=rs)
     tok = torch.cat([cls.to(dt).expand(B, 1, width), out.reshape(B, P, width)], 1) + pos
     ref = torch.nn.functional.layer_norm(tok.double(), (width,), gamma.double(), beta.double(), 1e-5)
     check(xt, ref.reshape(-1, width), tol(dt), "embed+ln_pre")
+    if rowsums:                                        # {sum, sum of squares} of every output row AS STORED (include/ffm_hip.h)
+        check(rs[:, 0], xt.double().sum(1), 1e-5, "row sums")
+        check(rs[:, 1], (xt.double() ** 2).sum(1), 1e-5, "row sums of squares")
+    guard.check()
 
 
 
@@ -413,7 +461,7 @@ def test_patchify_and_embed(ops, dt):
                                             (2, 16, 32, 8, 64),      # MAXD slices per group, one strip, ragged row blocks
                                             (2, 5, 40, 8, 64),       # a slice count that is no multiple of the 4 waves
                                             (1, 8, 224, 16, 768)])   # the bench geometry: 16 x 14-row / 4 x 56-row blocks
-def test_slice3d_front_end(ops, dt, N, D, H, ps, width):
+def test_slice3d_front_end(ops, guard, dt, N, D, H, ps, width):
     """conv5x5 + per-image min-max + patchify, and their backward down to the conv weight/bias gradient,
     against torch autograd in fp64 (trainers/GLP_OT_SVLoRA.py:681-693)."""
     F = torch.nn.functional
@@ -423,11 +471,11 @@ def test_slice3d_front_end(ops, dt, N, D, H, ps, width):
     mean3, std3 = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
     P = (H // ps) ** 2
     nblk = ops.slice_blocks(H, H)
-    conv = torch.empty(N, 3, H, H, device="cuda")
-    mm_part = torch.empty(N * nblk * 2, device="cuda")
-    mnmx = torch.empty(N, 2, device="cuda")
-    cnt = torch.full((N, 2), 77, device="cuda", dtype=torch.int32)
-    cols = torch.empty(N * P, 3 * ps * ps, device="cuda", dtype=dt)
+    conv = guard.out(N, 3, H, H)
+    mm_part = guard.scratch(N * nblk * 2)
+    mnmx = guard.out(N, 2)
+    cnt = guard.out(N, 2, dtype=torch.int32)
+    cols = guard.out(N * P, 3 * ps * ps, dtype=dt)
     ops.slice_conv_fwd(img, w, b, conv, mm_part, mnmx, cnt, D)
     ops.patchify_minmax(conv, mnmx, cnt, cols, ps, mean3, std3)
 
@@ -449,22 +497,27 @@ def test_slice3d_front_end(ops, dt, N, D, H, ps, width):
 
     dcols = rnd(N * P, 3 * ps * ps, dt=dt, seed=34)
     ref_cols.backward(dcols.double())
-    dconv = torch.empty_like(conv)
-    ab_part = torch.empty(N * ops.slice_bwd_ab_blocks() * 2, device="cuda")
-    gmm = torch.empty(N, 2, device="cuda")
+    dconv = guard.scratch(*conv.shape)                                # (scratch by the header: bands only)
+    ab_part = guard.scratch(N * ops.slice_bwd_ab_blocks() * 2)
+    gmm = guard.scratch(N, 2)
     nw = 3 * D * 25 + 3
     nwb = ops.slice_wgrad_blocks(H, H)
-    wpart = torch.full((N * nwb * nw,), float("nan"), device="cuda")          # every entry must be written
+    wpart = guard.out(N * nwb * nw)          # every entry must be written
     ops.slice_bwd(dcols, img, conv, mnmx, cnt, dconv, ab_part, gmm, wpart, D, ps, std3)
-    got = torch.empty(nw, device="cuda")
+    got = guard.out(nw)
     ops.reduce_partials(wpart, N * nwb, nw, got)
     check(got[:nw - 3].reshape(3, D, 5, 5), wd.grad, 2e-4, "slice conv dW")
     check(got[nw - 3:], bd.grad, 2e-4, "slice conv dbias")
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("B,P,width", [(3, 16, 128), (2, 196, 768), (2, 9, 1024), (2, 9, 1536)])
-def test_embed_lnpre_bwd(ops, dt, B, P, width):
+def test_embed_lnpre_bwd(ops, guard, dt, B, P, width):
+    embed_lnpre_bwd_case(ops, guard, dt, B, P, width)
+
+
+def embed_lnpre_bwd_case(ops, guard, dt, B, P, width):
     patch = rnd(B * P, width, dt=dt, seed=41)
     cls, pos = rnd(width, dt=dt, scale=0.1, seed=42), rnd(P + 1, width, dt=dt, scale=0.1, seed=43)
     gamma, beta = 1 + 0.1 * rnd(width, seed=44), 0.1 * rnd(width, seed=45)
@@ -473,9 +526,10 @@ def test_embed_lnpre_bwd(ops, dt, B, P, width):
     tok = torch.cat([cls.double().expand(B, 1, width), pd.reshape(B, P, width)], 1) + pos.double()
     y = torch.nn.functional.layer_norm(tok, (width,), gamma.double(), beta.double(), 1e-5)
     y.backward(dx.double().reshape(B, P + 1, width))
-    dpatch = torch.empty_like(patch)
+    dpatch = guard.like(patch)
     ops.embed_lnpre_bwd(dx, patch, pos, gamma, dpatch, B, P + 1)
     check(dpatch, pd.grad, tol(dt), "embed+ln_pre backward")
+    guard.check()
 
 
 # ------------------------------------------------------------- attention ---
@@ -493,11 +547,15 @@ def ref_attention(qkv, B, L, heads, causal):
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("B,L,heads,causal", [(2, 17, 2, False), (3, 197, 12, False), (4, 77, 8, True), (2, 64, 1, False),
                                                (1, 256, 2, True)])
-def test_attention_fwd_bwd(ops, dt, B, L, heads, causal):
+def test_attention_fwd_bwd(ops, guard, dt, B, L, heads, causal):
+    attention_case(ops, guard, dt, B, L, heads, causal)
+
+
+def attention_case(ops, guard, dt, B, L, heads, causal, whole_gradient=False):
     E = heads * 64
     qkv = rnd(B * L, 3 * E, dt=dt, seed=23)
-    out = torch.full((B * L, E), float("nan"), device="cuda", dtype=dt)
-    lse = torch.empty(B, heads, L, device="cuda")
+    out = guard.out(B * L, E, dtype=dt)
+    lse = guard.out(B, heads, L)
     ops.attention_fwd(qkv, out, lse, B, L, heads, causal)
     qd = qkv.double().requires_grad_(True)
     ref, ref_lse = ref_attention(qd, B, L, heads, causal)
@@ -505,13 +563,22 @@ def test_attention_fwd_bwd(ops, dt, B, L, heads, causal):
     check(lse, ref_lse.detach(), 1e-5 if dt == torch.float32 else 2e-3, "lse")
     dout = rnd(B * L, E, dt=dt, seed=24)
     ref.backward(dout.double())
-    dqkv = torch.full((B * L, 3 * E), float("nan"), device="cuda", dtype=dt)
-    delta = torch.empty(B, heads, L, device="cuda")
+    dqkv = guard.out(B * L, 3 * E, dtype=dt)
+    delta = guard.scratch(B, heads, L)                                # (scratch by the header: bands only)
     ops.attention_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, causal)
     t = tol(dt) * (1 if dt == torch.float32 else 2)
+    if whole_gradient:
+        # one token: dq and dk are exactly zero (softmax of one score), so they have no scale of their own - held to dv's
+        check(dqkv, qd.grad, t, "dqkv")
+        assert float(qd.grad[:, :2 * E].abs().max()) == 0.0                  # (the reference's dq, dk: exactly zero)
+        # ... the kernels form dP and delta in different summation orders, so theirs are zero to rounding: an absolute bound
+        assert float(dqkv[:, :2 * E].double().abs().max()) <= t * float(qd.grad[:, 2 * E:].abs().max()), "dq / dk at one token"
+        guard.check()
+        return
     check(dqkv[:, :E], qd.grad[:, :E], t, "dq")
     check(dqkv[:, E:2 * E], qd.grad[:, E:2 * E], t, "dk")
     check(dqkv[:, 2 * E:], qd.grad[:, 2 * E:], t, "dv")
+    guard.check()
 
 
 # ------------------------------------------------------------------ LoRA ---
@@ -534,17 +601,21 @@ def mix(attr, G, lam=0.7):
                                                       # down projection, u = dpre B_fc^T), ragged last block, 1..16 rank slots
                                                       (6304, 3072, 8, 3, 197, True, True), (2000, 768, 16, 2, 50, True, False),
                                                       (1030, 512, 5, 3, 197, True, True)])
-def test_lora_down(ops, dt, M, K, r, G, rps, rk, use_attr):
+def test_lora_down(ops, guard, dt, M, K, r, G, rps, rk, use_attr):
+    lora_down_case(ops, guard, dt, M, K, r, G, rps, rk, use_attr)
+
+
+def lora_down_case(ops, guard, dt, M, K, r, G, rps, rk, use_attr):
     x = rnd(M, K, dt=dt, seed=25)
     P = rnd(r, K, scale=0.1, seed=26) if rk else rnd(K, r, scale=0.1, seed=26)
     S = rnd(G, r, seed=27)
     nsamp = (M + rps - 1) // rps
     attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
-    t = torch.empty(M, r, device="cuda")
-    ts = torch.empty(M, r, device="cuda")
+    t = guard.out(M, r)
+    ts = guard.out(M, r)
     t_fwd = rnd(M, r, seed=28)
     nb = ops.lora_down_blocks(M, K, r, dt)
-    ds_part = torch.full((nb, G, r), float("nan"), device="cuda")
+    ds_part = guard.out(nb, G, r)
     ops.lora_down(x, P, rk, S, attr, r, G, rps, 0.25, 0.7, t, ts, t_fwd, ds_part)
     Pq = P.to(dt).double()                         # the kernel keeps P in the activation dtype in LDS
     Pm = Pq.t() if rk else Pq
@@ -557,44 +628,55 @@ def test_lora_down(ops, dt, M, K, r, G, rps, rk, use_attr):
     check(ts, 0.25 * ref_t * sb, 2e-5, "ts")
     ref_ds = pi_rows.t() @ (0.25 * t_fwd.double() * ref_t)
     check(ds_part.double().sum(0), ref_ds, 5e-5, "dS")
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("M,K,r", [(1000, 768, 8), (197, 3072, 16), (64, 128, 4), (130, 264, 32)])
-def test_lora_grad(ops, dt, M, K, r):
+def test_lora_grad(ops, guard, dt, M, K, r):
+    lora_grad_case(ops, guard, dt, M, K, r)
+
+
+def lora_grad_case(ops, guard, dt, M, K, r):
     x = rnd(M, K, dt=dt, seed=29)
     v = rnd(M, r, seed=30)
     ns = ops.lora_grad_splits(M)
-    part = torch.full((ns, K, r), float("nan"), device="cuda")
+    part = guard.out(ns, K, r)
     ops.lora_grad_partial(x, v, r, part)
     ref = x.double().t() @ v.double()
-    out = torch.empty(K, r, device="cuda")
+    out = guard.out(K, r)
     ops.reduce_partials(part, ns, K * r, out)
     check(out, ref, 3e-5, "dA-style [K,r]")
-    out_t = torch.empty(r, K, device="cuda")
+    out_t = guard.out(r, K)
     ops.reduce_partials(part, ns, K * r, out_t, transpose_K=K, transpose_r=r)
     check(out_t, ref.t(), 3e-5, "dB-style [r,K]")
     ops.reduce_partials(part, ns, K * r, out, accumulate=True)
     check(out, 2 * ref, 3e-5, "accumulate")
     # the batched form (one launch for many tensors)
-    o1, o2 = torch.zeros(K, r, device="cuda"), torch.zeros(r, K, device="cuda")
+    o1, o2 = guard.out(K, r), guard.out(r, K)
     plan = ops.ReducePlan([(part, ns, K * r, o1, 0, 0), (part, ns, K * r, o2, K, r)], "cuda")
     plan.run()
     check(o1, ref, 3e-5, "multi [K,r]")
     check(o2, ref.t(), 3e-5, "multi [r,K]")
+    guard.check()
 
 
 # ------------------------------------------------------------------ head ---
 @pytest.mark.parametrize("dt", DT, ids=IDS)
 @pytest.mark.parametrize("B,L,D,S", [(8, 197, 512, 1), (6, 17, 128, 2)])
-def test_head_and_loss(ops, dt, B, L, D, S):
-    n_cls = 2
+def test_head_and_loss(ops, guard, dt, B, L, D, S):
+    head_and_loss_case(ops, guard, dt, B, L, D, S)
+
+
+def head_and_loss_case(ops, guard, dt, B, L, D, S, n_cls=2, zero_row=None):
     f = rnd(B * L, D, dt=dt, seed=31)
+    if zero_row is not None:
+        f[zero_row] = 0                                               # the 1e-12 clamp of F.normalize, forward and backward
     tbar = rnd(n_cls, D, scale=D ** -0.5, seed=32)
     ls = torch.tensor([math.log(1 / 0.07)], device="cuda")
-    fbar = torch.empty(B, D, device="cuda")
-    rnorm = torch.empty(B * L, device="cuda")
-    logits_img = torch.empty(B, n_cls, device="cuda")
+    fbar = guard.out(B, D)
+    rnorm = guard.out(B * L)
+    logits_img = guard.out(B, n_cls)
     ops.head_fwd(f, tbar, ls, fbar, rnorm, logits_img, B, L, n_cls)
     fd = f.double().requires_grad_(True)
     td = tbar.double().requires_grad_(True)
@@ -603,11 +685,11 @@ def test_head_and_loss(ops, dt, B, L, D, S):
     check(logits_img, ref_img.detach(), 2e-5 if dt == torch.float32 else 1e-4, "logits_img")
     nb = B // S
     label = torch.randint(0, n_cls, (nb,), device="cuda")
-    logits = torch.empty(nb, n_cls, device="cuda")
-    prob = torch.empty(nb, n_cls, device="cuda")
-    loss = torch.empty(1, device="cuda")
-    dl = torch.empty(B, n_cls, device="cuda")
-    fin = torch.zeros(1, device="cuda", dtype=torch.int32)
+    logits = guard.out(nb, n_cls)
+    prob = guard.out(nb, n_cls)
+    loss = guard.out(1)
+    dl = guard.out(B, n_cls)
+    fin = guard.out(1, dtype=torch.int32)
     ops.ce_loss(logits_img, label, logits, prob, loss, dl, fin, nb, S, n_cls)
     ref_logits = ref_img.reshape(nb, S, n_cls).mean(1)
     ref_loss = torch.nn.functional.cross_entropy(ref_logits, label)
@@ -616,11 +698,25 @@ def test_head_and_loss(ops, dt, B, L, D, S):
     assert int(fin) == 1
     check(prob, torch.softmax(ref_logits, -1).detach(), 1e-4, "prob")
     ref_loss.backward()
-    df = torch.empty_like(f)
-    dtbar = torch.empty_like(tbar)
+    df = guard.like(f)
+    dtbar = guard.like(tbar)
     ops.head_bwd(f, tbar, ls, fbar, rnorm, dl, df, dtbar, B, L, n_cls)
-    check(df, fd.grad, 2e-4 if dt == torch.float32 else 1.5e-2, "df")
+    t_df = 2e-4 if dt == torch.float32 else 1.5e-2
+    if zero_row is None:
+        check(df, fd.grad, t_df, "df")
+    else:
+        # the clamped row's gradient is dL/dy / 1e-12: held on its own (it would set the scale for every other row), and where
+        # it does not fit the storage type (IEEE half) it must be the infinity the rounded reference is
+        rows = torch.ones(B * L, dtype=torch.bool, device="cuda")
+        rows[zero_row] = False
+        check(df[rows], fd.grad[rows], t_df, "df of the other rows")
+        want = fd.grad[zero_row].to(dt)
+        inf = torch.isinf(want)
+        assert torch.equal(df[zero_row][inf], want[inf]), "df of the all-zero row where 1e12 dL/dy overflows the storage type"
+        if bool((~inf).any()):
+            check(df[zero_row][~inf], fd.grad[zero_row][~inf], t_df, "df of the all-zero row")
     check(dtbar, td.grad, 2e-4 if dt == torch.float32 else 1e-3, "dtbar")
+    guard.check()
 
 
 # ----------------------------------------------------------- optimizer ----
@@ -673,10 +769,10 @@ def test_fedavg_aggregator_gpu_equals_cpu():
     assert torch.equal(blk[0, : r // 2], blk[1, : r // 2]) and not torch.equal(blk[0, r // 2:], blk[1, r // 2:])
 
 
-def test_fedavg_helpers(ops):
+def test_fedavg_helpers(ops, guard):
     G, r, n = 3, 8, 1000
     p, w = rnd(n, seed=40), torch.rand(n, device="cuda")
-    out = torch.empty(n, device="cuda")
+    out = guard.out(n)
     ops.scale_by(p, w, out)
     assert torch.allclose(out, p * w)
     # the second client of a rank: acc += p2 * w2 with the product and the sum rounded separately (bit-exact vs torch)
@@ -691,13 +787,14 @@ def test_fedavg_helpers(ops):
         blk = ref[o:o + G * r].view(G, r)
         blk[:, : r // 2] = blk[:, : r // 2].mean(0, keepdim=True)
     ref = (1 - 0.3) * ref + 0.3 * prev
-    res = torch.empty(n, device="cuda")
+    res = guard.out(n)
     ops.fedavg_finish(avg, prev, res, offs, G, r, True, 0.3)
     check(res, ref, 1e-6, "fedavg_finish")
     # in place on the previous global (what FedAvgAggregator.finish does): same values
     prev2 = prev.clone()
     ops.fedavg_finish(avg.clone(), prev2, prev2, offs, G, r, True, 0.3)
     assert torch.equal(prev2, res)
+    guard.check()
 
 
 def test_casts(ops):
@@ -719,7 +816,7 @@ def test_casts_half(ops):
 @pytest.mark.parametrize("M,N,K", [(40, 1536, 512), (40, 512, 2048), (40, 2048, 512), (1, 512, 128), (64, 128, 128),
                                    (33, 48, 640), (8, 512, 512)])
 @pytest.mark.parametrize("mode", ["plain", "bias", "bias_res", "bias_gelu", "dgelu"])
-def test_skinny_gemm_text_tower_shapes(M, N, K, mode):
+def test_skinny_gemm_text_tower_shapes(guard, M, N, K, mode):
     """gemm_skinny.hip (M <= 64 rows, bf16): the text tower's products and epilogues against fp32 PyTorch on the same
     bf16 operands; split-K over four waves must not change the result beyond fp32 summation order."""
     from fairfedmed_amd import ops
@@ -729,8 +826,8 @@ def test_skinny_gemm_text_tower_shapes(M, N, K, mode):
     bias = torch.randn(N, device="cuda", generator=g)
     res = torch.randn(M, N, device="cuda", generator=g).to(torch.bfloat16)
     aux = torch.randn(M, N, device="cuda", generator=g).to(torch.bfloat16)
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
-    act = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guard.out(M, N, dtype=torch.bfloat16)
+    act = guard.out(M, N, dtype=torch.bfloat16) if mode == "bias_gelu" else None                    # (the second output exists under the GELU epilogue only)
     ref = a.float() @ w.float().t()
     rel = lambda got, want: float((got.double() - want.double()).abs().max() / want.double().abs().max())
     if mode == "plain":
@@ -751,11 +848,12 @@ def test_skinny_gemm_text_tower_shapes(M, N, K, mode):
         s = torch.sigmoid(1.702 * x)
         ref = ref * (s * (1 + 1.702 * x * (1 - s)))
     assert rel(out.float(), ref) < 1e-2                              # bf16 rounding of the output only
+    guard.check()
 
 
 @pytest.mark.parametrize("M,N,K", [(33, 48, 640), (8, 512, 512)], ids=["4waves", "8waves"])
 @pytest.mark.parametrize("mode", ["plain", "bias", "bias_res", "bias_gelu", "dgelu"])
-def test_skinny_gemm_half(M, N, K, mode):
+def test_skinny_gemm_half(guard, M, N, K, mode):
     """test_skinny_gemm_text_tower_shapes in IEEE half (the half twin of gemm_skinny.hip), at its two smallest shapes that
     take the four-wave and the eight-wave split of K; fp64 reference on the same half operands, bound tol(float16)."""
     from fairfedmed_amd import ops
@@ -766,8 +864,8 @@ def test_skinny_gemm_half(M, N, K, mode):
     bias = torch.randn(N, device="cuda", generator=g)
     res = torch.randn(M, N, device="cuda", generator=g).to(dt)
     aux = torch.randn(M, N, device="cuda", generator=g).to(dt)
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
-    act = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
+    out = guard.out(M, N, dtype=dt)
+    act = guard.out(M, N, dtype=dt) if mode == "bias_gelu" else None
     ref = a.double() @ w.double().t()
     if mode == "plain":
         ops.gemm_nt(a, w, out)
@@ -787,13 +885,14 @@ def test_skinny_gemm_half(M, N, K, mode):
         s = torch.sigmoid(1.702 * x)
         ref = ref * (s * (1 + 1.702 * x * (1 - s)))
     check(out, ref, tol(dt), "skinny " + mode)
+    guard.check()
 
 
 @pytest.mark.parametrize("M,N,K", [(40, 1536, 512), (40, 512, 2048), (40, 2048, 512), (1, 512, 128), (64, 128, 128),
                                    (33, 48, 640), (8, 512, 512)])
 @pytest.mark.parametrize("x3", [True, False, "w16"], ids=["x3", "exact", "x3w16"])
 @pytest.mark.parametrize("mode", ["plain", "bias", "bias_res", "bias_gelu", "dgelu"])
-def test_skinny_gemm_f32(M, N, K, x3, mode):
+def test_skinny_gemm_f32(guard, M, N, K, x3, mode):
     """The text tower's products in float32 (engine.py: always, also beside a bf16 vision tower): FFM_F32_X3 (operands
     split into bf16 hi + lo pairs, three MFMAs at the bf16 rate), the same on a weight stored as IEEE half
     (FFM_F32_X3_W16: the half value is split exactly, so the reference is float64 on the ROUNDED weight at the same
@@ -807,8 +906,8 @@ def test_skinny_gemm_f32(M, N, K, x3, mode):
     bias = torch.randn(N, device="cuda", generator=g)
     res = torch.randn(M, N, device="cuda", generator=g)
     aux = torch.randn(M, N, device="cuda", generator=g)
-    out = torch.full((M, N), float("nan"), device="cuda")
-    act = torch.full((M, N), float("nan"), device="cuda")
+    out = guard.out(M, N)
+    act = guard.out(M, N) if mode == "bias_gelu" else None
     ref = a.double() @ w.double().t()
     rel = lambda got, want: float((got.double() - want.double()).abs().max() / want.double().abs().max())
     # hi + lo keeps 16 significant bits of every operand (2^-16 per product, the lo*lo term is dropped); after the sum
@@ -834,12 +933,13 @@ def test_skinny_gemm_f32(M, N, K, x3, mode):
         tol = max(tol, 1e-5)
     assert not torch.isnan(out).any()
     assert rel(out, ref) < tol, rel(out, ref)
+    guard.check()
 
 
 @pytest.mark.parametrize("M,N,K", [(40, 512, 2048), (40, 512, 1536), (40, 2048, 512), (40, 1536, 512), (33, 512, 1024), (48, 256, 2048), (1, 512, 2048)])
 @pytest.mark.parametrize("w16", [False, True], ids=["x3", "x3w16"])
 @pytest.mark.parametrize("mode", ["plain", "bias", "bias_res", "bias_gelu", "dgelu"])
-def test_skinny_gemm_split_over_k(M, N, K, w16, mode):
+def test_skinny_gemm_split_over_k(guard, M, N, K, w16, mode):
     """ffm_gemm_args.sk_part (ABI 12): the text tower's narrow products split over K across the grid - partial tiles per
     128-deep slice, summed in slice order by the finish launch with the one-launch kernel's epilogues.  Against float64 at the
     X3 tolerance, bit-identical from run to run (no atomics), and the scratch query says which products are split."""
@@ -854,13 +954,13 @@ def test_skinny_gemm_split_over_k(M, N, K, w16, mode):
     aux = torch.randn(M, N, device="cuda", generator=g)
     need = ops.gemm_splitk_floats(M, N, K, w16)
     assert need == (K // 128) * M * N and ops.gemm_splitk_floats(M, 4096, 512, w16) == 0 and ops.gemm_splitk_floats(64, N, K, w16) == 0 and ops.gemm_splitk_floats(M, N, 256, w16) == 0
-    part = torch.full((need,), float("nan"), device="cuda")
+    part = guard.scratch(need)                                         # exactly the queried size; partial tiles: scratch
     rel = lambda got, want: float((got.double() - want.double()).abs().max() / want.double().abs().max())
     ref = a.double() @ w.double().t()
     outs = []
     for _ in range(2):
-        out = torch.full((M, N), float("nan"), device="cuda")
-        act = torch.full((M, N), float("nan"), device="cuda")
+        out = guard.out(M, N)
+        act = guard.out(M, N) if mode == "bias_gelu" else None
         kw = {"plain": {}, "bias": dict(bias=bias), "bias_res": dict(bias=bias, res=res), "bias_gelu": dict(bias=bias, gelu_out=act),
               "dgelu": dict(dgelu_aux=aux)}[mode]
         ops.gemm_nt(a, w, out, x3=True, sk_part=part, **kw)
@@ -881,16 +981,17 @@ def test_skinny_gemm_split_over_k(M, N, K, w16, mode):
     assert not torch.isnan(out).any()
     assert rel(out, ref) < tol, rel(out, ref)
     # the one-launch kernel on the same operands: same value to the fp32 summation order
-    one = torch.empty_like(out)
-    kw = {"plain": {}, "bias": dict(bias=bias), "bias_res": dict(bias=bias, res=res), "bias_gelu": dict(bias=bias, gelu_out=torch.empty_like(out)),
+    one = guard.like(out)
+    kw = {"plain": {}, "bias": dict(bias=bias), "bias_res": dict(bias=bias, res=res), "bias_gelu": dict(bias=bias, gelu_out=guard.like(out) if mode == "bias_gelu" else None),
           "dgelu": dict(dgelu_aux=aux)}[mode]
     ops.gemm_nt(a, w, one, x3=True, **kw)
     assert rel(out, one) < 5e-6
+    guard.check()
 
 
 @pytest.mark.parametrize("M,r,G,use_attr", [(6304, 8, 3, True), (6250, 12, 2, False), (6304, 16, 3, True), (5000, 4, 3, True), (3000, 8, 3, True)])
 @H16
-def test_gemm_panel_layernorm_backward_fold(ops, M, r, G, use_attr, h16):
+def test_gemm_panel_layernorm_backward_fold(ops, guard, M, r, G, use_attr, h16):
     """FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (ABI 12): ln_2's backward folded into the two dX products of the MLP.
     (1) the dX product of c_proj leaves sum_n dpre pre per row and column tile (packed 16-bit dot products) - float64 on the
     16-bit rows it stored - and nothing else it writes moves; (2) the dX product of c_fc, whose rank operand carries W gamma and
@@ -900,10 +1001,10 @@ def test_gemm_panel_layernorm_backward_fold(ops, M, r, G, use_attr, h16):
     rps = 197
     nsamp = (M + rps - 1) // rps
     attr = torch.randint(0, G, (nsamp,), device="cuda", dtype=torch.int32) if use_attr else None
-    panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, h16)
+    panel_layernorm_backward_fold_case(ops, guard, M, r, G, attr, rps, h16)
 
 
-def panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, dt, before_checks=None):
+def panel_layernorm_backward_fold_case(ops, guard, M, r, G, attr, rps, dt, before_checks=None):
     """Body of test_gemm_panel_layernorm_backward_fold for a given attribute vector and rows per sample.  `before_checks`
     (as in panel_fairlora_case) is called twice: for the LNB_STAT launch (rank operand P2 / S2) and for the LNB_APPLY
     launch (rank operand B_fc / S, whose ts is `us`; that launch stores no t)."""
@@ -947,15 +1048,15 @@ def panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, dt, before_check
     bp = ops.pack_b(Wpt)
 
     def run1(stat):
-        out = torch.empty(M, N, device="cuda", dtype=dt)
-        t, ts = torch.full((M, r), float("nan"), device="cuda"), torch.full((M, r), float("nan"), device="cuda")
-        dsp = torch.full((nrows, G, r), float("nan"), device="cuda")
-        pc, pa = torch.full((nlg, N, r), float("nan"), device="cuda"), torch.full((nlg, N, r), float("nan"), device="cuda")
+        out = guard.out(M, N, dtype=dt)
+        t, ts = guard.out(M, r), guard.out(M, r)
+        dsp = guard.out(nrows, G, r)
+        pc, pa = guard.out(nlg, N, r), guard.out(nlg, N, r)
         ro = ops.RankOp(rk2, S2, attr, rps, sigma, 0.7, t_out=t, ts_out=ts, t_fwd=t_fwd, ds_part=dsp, lgrad=(ts1, pc, pa))
         ops.gemm_nt(gi, Wpt, out, lw=lw2, lw_is_kr=True, rankop=ro, b_packed=bp, dgelu_aux=pre, lnb_stat=stat)
         return out, t, ts, dsp, pc, pa
 
-    part = torch.full((tn, M, 2), float("nan"), device="cuda")
+    part = guard.out(tn, M, 2)
     got = run1(ops.LnBwdStat(part))
     base = run1(None)
     for a_, b_ in zip(got, base):
@@ -988,9 +1089,9 @@ def panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, dt, before_check
     bp2 = ops.pack_b(Wfct)
 
     def run2(apply):
-        out = torch.full((M, K), float("nan"), device="cuda", dtype=dt)
-        us = torch.full((M, r), float("nan"), device="cuda")
-        dsp = torch.full((nrows2, G, r), float("nan"), device="cuda")
+        out = guard.out(M, K, dtype=dt)
+        us = guard.out(M, r)
+        dsp = guard.out(nrows2, G, r)
         ro = ops.RankOp(rk1, S, attr, rps, sigma, 0.7, ts_out=us, t_fwd=t_fwd1, ds_part=dsp)
         ops.gemm_nt(dpre, Wfct, out, lw=A, lw_is_kr=True, rankop=ro, b_packed=bp2, lnb_apply=apply)
         return out, us, dsp
@@ -1015,17 +1116,22 @@ def panel_layernorm_backward_fold_case(ops, M, r, G, attr, rps, dt, before_check
     ref = xd.grad + gres.double()
     check(g1, ref, tol(dt), "folded LayerNorm backward vs float64 autograd")
     # the unfolded pair: plain dX product (g_h rounded to 16 bits), then ffm_layernorm_bwd with the residual
-    g1u = torch.empty(M, K, device="cuda", dtype=dt)
+    g1u = guard.out(M, K, dtype=dt)
     ops.layernorm_bwd(gh, x, gamma, mean32, rstd32, gres, g1u)
     check(g1, g1u.double(), 2 * tol(dt), "against the unfolded pair")
     # ... and the fold is the closer of the two to float64 (g_h is never rounded to 16 bits on its way)
     err = lambda t_: float((t_.double() - ref).abs().max() / ref.abs().max())
     print("LayerNorm backward fold: max error vs float64", err(g1), " unfolded pair", err(g1u))
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
 @pytest.mark.parametrize("B,L,heads", [(32, 197, 12), (5, 197, 12), (3, 130, 4), (2, 256, 12)])
-def test_attention_backward_layernorm_row_sums_and_plain_apply(ops, dt, B, L, heads):
+def test_attention_backward_layernorm_row_sums_and_plain_apply(ops, guard, dt, B, L, heads):
+    attention_lnstat_case(ops, guard, dt, B, L, heads)
+
+
+def attention_lnstat_case(ops, guard, dt, B, L, heads):
     """ln_1's backward folded (ABI 12): ffm_attention_bwd_lnstat leaves, per head, {sum dqkv (W gamma), sum dqkv (qkv - d)} over
     the head's q columns (dQ kernel) and its k and v columns (dK/dV kernel) - float64 on the 16-bit dqkv it stored, which must
     be bit-identical to the plain call's; the dX product of the in-projection with FFM_EPI_LNB_APPLY then stores
@@ -1042,17 +1148,17 @@ def test_attention_backward_layernorm_row_sums_and_plain_apply(ops, dt, B, L, he
     h = (xd - mu) * rstd * gamma.double() + beta.double()
     qkv64 = h @ W.double().t() + bias.double()
     qkv = qkv64.detach().to(dt).contiguous()
-    out = torch.empty(M, E, device="cuda", dtype=dt)
-    lse = torch.empty(B, heads, L, device="cuda")
+    out = guard.out(M, E, dtype=dt)
+    lse = guard.out(B, heads, L)
     ops.attention_fwd(qkv, out, lse, B, L, heads, False)
     dout = rnd(M, E, dt=dt, seed=406)
-    delta = torch.empty(B, heads, L, device="cuda")
-    dq0 = torch.full((M, 3 * E), float("nan"), device="cuda", dtype=dt)
+    delta = guard.scratch(B, heads, L)
+    dq0 = guard.out(M, 3 * E, dtype=dt)
     ops.attention_bwd(qkv, out, dout, lse, delta, dq0, B, L, heads, False)
     wg = (W.double() @ gamma.double()).float().contiguous()
     dvec = (W.double() @ beta.double() + bias.double()).float().contiguous()
-    part = torch.full((2 * heads, M, 2), float("nan"), device="cuda")
-    dqkv = torch.full((M, 3 * E), float("nan"), device="cuda", dtype=dt)
+    part = guard.out(2 * heads, M, 2)
+    dqkv = guard.out(M, 3 * E, dtype=dt)
     ops.attention_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, False, ln_stat=(wg, dvec, part))
     assert torch.equal(dqkv, dq0), "the row sums must not move dqkv"
     assert not torch.isnan(part).any()
@@ -1067,21 +1173,23 @@ def test_attention_backward_layernorm_row_sums_and_plain_apply(ops, dt, B, L, he
         check(part[heads + hh, :, 1], kv(t2), 1e-5, f"k, v columns of head {hh}: sum dqkv (qkv - d)")
     # the consumer: dX of the in-projection, [M, 3E] x [E, 3E]^T
     if E % 128 or ops.gemm_tiles_n(M, E, 3 * E, 4096, 0, dt, True) <= 0:
+        guard.check()
         return                                                          # (no plain panel tile for this shape: the engine asks too)
     Wt = W.t().contiguous()
     gres = rnd(M, E, dt=dt, seed=407)
     mean32, rstd32 = mu.detach().float().reshape(-1).contiguous(), rstd.detach().float().reshape(-1).contiguous()
-    g1 = torch.full((M, E), float("nan"), device="cuda", dtype=dt)
+    g1 = guard.out(M, E, dtype=dt)
     ops.gemm_nt(dqkv, Wt, g1, b_packed=ops.pack_b(Wt),
                 lnb_apply=ops.LnBwdApply(part, 2 * heads, x, gamma, mean32, rstd32, None, gres))
     (qkv64 * dqkv.double()).sum().backward()
     ref = xd.grad + gres.double()
     check(g1, ref, tol(dt), "folded ln_1 backward vs float64 autograd")
-    gh = torch.empty(M, E, device="cuda", dtype=dt)
+    gh = guard.out(M, E, dtype=dt)
     ops.gemm_nt(dqkv, Wt, gh, b_packed=ops.pack_b(Wt))
-    g1u = torch.empty(M, E, device="cuda", dtype=dt)
+    g1u = guard.out(M, E, dtype=dt)
     ops.layernorm_bwd(gh, x, gamma, mean32, rstd32, gres, g1u)
     check(g1, g1u.double(), 2 * tol(dt), "against the unfolded pair")
+    guard.check()
 
 
 def test_skinny_x3_tiles_per_block_switch():
@@ -1137,21 +1245,25 @@ def test_x3_gemm_rejects_large_products():
 # ------------------------------------------------ LayerNorm folded into the GEMMs around it ---
 @pytest.mark.mask_tolerant
 @H16
-def test_gemm_rowstats_partials(h16):
+def test_gemm_rowstats_partials(guard, h16):
+    rowstats_case(guard, h16, 6304)
+
+
+def rowstats_case(guard, h16, M):
     """FFM_EPI_ROWSTATS (out-proj forward shape): the partial {sum, sum of squares} of every STORED output row, one
     partial per column tile, add up to the row sums of the bf16 output."""
     from fairfedmed_amd import ops, _lib as L
-    M, N, K = 6304, 768, 768
+    N, K = 768, 768
     g = torch.Generator(device="cuda").manual_seed(5)
     a = torch.randn(M, K, device="cuda", generator=g).to(h16)
     w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).to(h16)
     bias = torch.randn(N, device="cuda", generator=g)
     res = (3 + torch.randn(M, N, device="cuda", generator=g)).to(h16)
-    out = torch.empty(M, N, device="cuda", dtype=h16)
+    out = guard.out(M, N, dtype=h16)
     bp = ops.pack_b(w)
     tn = ops.gemm_tiles_n(M, N, K, L.EPI_BIAS | L.EPI_RESIDUAL | L.EPI_ROWSTATS, 0, h16, True)
     assert tn > 0
-    part = torch.full((tn, M, 2), float("nan"), device="cuda")
+    part = guard.out(tn, M, 2)
     ops.gemm_nt(a, w, out, bias=bias, res=res, b_packed=bp, rowstats=part)
     ref = a.float() @ w.float().t() + bias + res.float()
     assert float((out.float() - ref).abs().max() / ref.abs().max()) < 1e-2
@@ -1163,16 +1275,21 @@ def test_gemm_rowstats_partials(h16):
     # without the packed weight no kernel serves the flag: refused, not computed some other way
     with pytest.raises(RuntimeError):
         ops.gemm_nt(a, w, out, bias=bias, res=res, rowstats=part)
+    guard.check()
 
 
 @pytest.mark.mask_tolerant
 @pytest.mark.parametrize("np_", [1, 6])
 @H16
-def test_gemm_layernorm_folded_in(np_, h16):
+def test_gemm_layernorm_folded_in(guard, np_, h16):
+    layernorm_folded_in_case(guard, np_, h16, 6304)
+
+
+def layernorm_folded_in_case(guard, np_, h16, M):
     """FFM_EPI_LNIN (qkv forward shape): raw rows x gamma-scaled weight, corrected in the epilogue with the row statistics
     assembled from np partial sums, equals LayerNorm(x) W^T + b; mean / rstd come out for the LayerNorm backward."""
     from fairfedmed_amd import ops
-    M, N, K = 6304, 2304, 768
+    N, K = 2304, 768
     g = torch.Generator(device="cuda").manual_seed(6)
     x = (1.5 + 2.0 * torch.randn(M, K, device="cuda", generator=g)).to(h16)     # a row mean far from 0
     x[:, 5] += 40.0                                                                          # one outlier channel
@@ -1186,9 +1303,9 @@ def test_gemm_layernorm_folded_in(np_, h16):
     xf = x.float()
     cols = torch.tensor_split(torch.arange(K, device="cuda"), np_)
     part = torch.stack([torch.stack([xf[:, ix].sum(1), (xf[:, ix] ** 2).sum(1)], 1) for ix in cols]).contiguous()
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=h16)
-    mean = torch.empty(M, device="cuda")
-    rstd = torch.empty(M, device="cuda")
+    out = guard.out(M, N, dtype=h16)
+    mean = guard.out(M)
+    rstd = guard.out(M)
     ops.gemm_nt(x, wg, out, bias=d, b_packed=ops.pack_b(wg), ln_in=ops.LnIn(part, np_, c, mean, rstd))
     xd = x.double()
     mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
@@ -1197,23 +1314,28 @@ def test_gemm_layernorm_folded_in(np_, h16):
     assert float((mean.double() - mu[:, 0]).abs().max()) < 1e-4
     assert float((rstd.double() * torch.sqrt(var[:, 0] + 1e-5) - 1).abs().max()) < 1e-4
     # against the unfolded bf16 path (LayerNorm kernel, then the product): the folded form is no less accurate
-    h = torch.empty_like(x)
-    ops.layernorm_fwd(x, h, gamma, beta, torch.empty(M, device="cuda"), torch.empty(M, device="cuda"))
+    h = guard.like(x)
+    ops.layernorm_fwd(x, h, gamma, beta, guard.out(M), guard.out(M))
     wb = w.to(h16)
-    out2 = torch.empty_like(out)
+    out2 = guard.like(out)
     ops.gemm_nt(h, wb, out2, bias=bias, b_packed=ops.pack_b(wb))
     e_fold = float((out.double() - ref).abs().mean())
     e_plain = float((out2.double() - ref).abs().mean())
     print(f"mean abs error: folded {e_fold:.3e}, LayerNorm kernel + GEMM {e_plain:.3e}")
     assert e_fold < 1.5 * e_plain
+    guard.check()
 
 
 @H16
-def test_lora_grad_partial_through_a_folded_layernorm(h16):
+def test_lora_grad_partial_through_a_folded_layernorm(guard, h16):
+    lora_grad_partial_ln_case(guard, h16, 6304)
+
+
+def lora_grad_partial_ln_case(guard, h16, M):
     """ffm_lora_grad_partial_ln: dA = LayerNorm(x)^T v from the RAW rows (the normalised copy is never written when ln_2
     rides inside the c_fc product) equals the plain reduction on a materialised LayerNorm output."""
     from fairfedmed_amd import ops
-    M, K, r = 6304, 768, 8
+    K, r = 768, 8
     g = torch.Generator(device="cuda").manual_seed(9)
     x = (0.7 + 1.5 * torch.randn(M, K, device="cuda", generator=g)).to(h16)
     v = torch.randn(M, r, device="cuda", generator=g)
@@ -1223,13 +1345,14 @@ def test_lora_grad_partial_through_a_folded_layernorm(h16):
     mu, var = xd.mean(1), xd.var(1, unbiased=False)
     rstd = 1 / torch.sqrt(var + 1e-5)
     ns = ops.lora_grad_splits(M)
-    part = torch.full((ns, K, r), float("nan"), device="cuda")
+    part = guard.out(ns, K, r)
     ops.lora_grad_partial_ln(x, v, mu.float(), rstd.float(), gamma, beta, r, part)
     got = part.double().sum(0)
     y = (xd - mu[:, None]) * rstd[:, None] * gamma.double() + beta.double()
     ref = y.t() @ v.double()
     assert not torch.isnan(part).any()
     assert float((got - ref).abs().max() / ref.abs().max()) < 2e-4      # v enters as a bf16 hi + lo pair
+    guard.check()
 
 
 def test_reduce_partials_many_rows_of_a_short_tensor():
@@ -1251,14 +1374,18 @@ def test_reduce_partials_many_rows_of_a_short_tensor():
 # ------------------------------------------------------ text tower's two ends ---
 @pytest.mark.parametrize("use_ot", [False, True], ids=["mean-over-prompts", "per-prompt"])
 @pytest.mark.parametrize("N,n_cls,n_ctx,TL,w,D", [(2, 2, 4, 10, 512, 512), (3, 2, 2, 7, 128, 192)])
-def test_text_tower_ends_vs_autograd(ops, use_ot, N, n_cls, n_ctx, TL, w, D):
+def test_text_tower_ends_vs_autograd(ops, guard, use_ot, N, n_cls, n_ctx, TL, w, D):
+    text_tower_ends_case(ops, guard, use_ot, N, n_cls, n_ctx, TL, w, D)
+
+
+def text_tower_ends_case(ops, guard, use_ot, N, n_cls, n_ctx, TL, w, D):
     """csrc/text.hip against the PyTorch statement of the same ops (trainers/GLP_OT_SVLoRA.py:131-152, 55-66, 713-717):
     prompt assembly + positional embedding; EOT gather -> ln_final -> projection -> normalise (-> mean over prompts);
     their backward down to the tower's output rows; d ctx summed over the classes."""
     n_text = N * n_cls
     prefix, suffix = rnd(n_text, 1, w, seed=1), rnd(n_text, 20, w, seed=2)
     ctx, pos = rnd(N, n_ctx, w, seed=3), rnd(TL + 5, w, seed=4)
-    x0 = torch.full((n_text * TL, w), float("nan"), device="cuda")
+    x0 = guard.out(n_text * TL, w)
     ops.text_embed(prefix, ctx, suffix, pos, x0, n_cls, TL)
     ctx_rows = ctx.unsqueeze(1).expand(N, n_cls, n_ctx, w).reshape(n_text, n_ctx, w)
     ref0 = torch.cat([prefix, ctx_rows, suffix[:, :TL - 1 - n_ctx]], dim=1) + pos[:TL]
@@ -1268,9 +1395,9 @@ def test_text_tower_ends_vs_autograd(ops, use_ot, N, n_cls, n_ctx, TL, w, D):
     eot_pos = [TL - 1 - (i % n_cls) for i in range(n_text)]
     eot_row = torch.tensor([i * TL + e for i, e in enumerate(eot_pos)], device="cuda", dtype=torch.int32)
     lnw, lnb, proj = 1 + 0.1 * rnd(w, seed=6), 0.1 * rnd(w, seed=7), rnd(w, D, seed=8) * w ** -0.5
-    tf, tn = torch.empty(n_text, D, device="cuda"), torch.empty(n_text, D, device="cuda")
-    rn, st = torch.empty(n_text, device="cuda"), torch.empty(n_text, 2, device="cuda")
-    tbar = None if use_ot else torch.empty(n_cls, D, device="cuda")
+    tf, tn = guard.out(n_text, D), guard.out(n_text, D)
+    rn, st = guard.out(n_text), guard.out(n_text, 2)
+    tbar = None if use_ot else guard.out(n_cls, D)
     ops.text_tail_fwd(x, eot_row, lnw, lnb, proj, tf, tn, rn, st, tbar, N, n_cls)
     xd = x.double().requires_grad_(True)
     xe = xd[eot_row.long()]
@@ -1285,8 +1412,8 @@ def test_text_tower_ends_vs_autograd(ops, use_ot, N, n_cls, n_ctx, TL, w, D):
     # tail backward
     dout = rnd(*out_ref.shape, seed=9)
     out_ref.backward(dout.double())
-    g = torch.full((n_text * TL, w), float("nan"), device="cuda")
-    dy = torch.empty(n_text, w, device="cuda")
+    g = guard.out(n_text * TL, w)
+    dy = guard.out(n_text, w)
     ops.text_tail_bwd(x, eot_row, lnw, proj, tn, rn, st, None if use_ot else dout, dout if use_ot else None, dy, g, N, n_cls, TL)
     check(g, xd.grad, 5e-6, "d(tower output)")
     rows = torch.ones(n_text * TL, dtype=torch.bool, device="cuda")
@@ -1294,10 +1421,11 @@ def test_text_tower_ends_vs_autograd(ops, use_ot, N, n_cls, n_ctx, TL, w, D):
     assert float(g[rows].abs().max()) == 0.0                               # every non-EOT row is exactly zero
     # d ctx = input-gradient rows 1 .. n_ctx of every prompt, summed over the classes
     gin = rnd(n_text * TL, w, seed=10)
-    dctx = torch.empty(N, n_ctx, w, device="cuda")
+    dctx = guard.out(N, n_ctx, w)
     ops.text_ctx_grad(gin, dctx, n_cls, TL)
     refc = gin.double().view(N, n_cls, TL, w)[:, :, 1:1 + n_ctx, :].sum(1)
     check(dctx, refc, 1e-6, "dctx")
+    guard.check()
 
 
 @pytest.mark.parametrize("mask,what", [(0, "the round-2 tiles only (configurations 0-4)"),
@@ -1314,7 +1442,7 @@ def test_panel_tile_configurations_behind_the_mask(mask, what):
     env = dict(os.environ, FFM_PANEL_MASK=str(mask))
     # no -x in the child: the tail then names every failure, not just the first
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-rfE", os.path.join(root, "tests", "test_kernels_gpu.py"),
-                        os.path.join(root, "tests", "test_group_mix_gpu.py"), "-m",
+                        os.path.join(root, "tests", "test_group_mix_gpu.py"), os.path.join(root, "tests", "test_guard_bands_gpu.py"), "-m",
                         "mask_tolerant"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "deselected" in r.stdout
@@ -1343,12 +1471,12 @@ A3_LENGTHS = [65, 96, 97, 113, 128, 129, 144, 160, 161, 176, 192, 193, 197, 200,
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
 @pytest.mark.parametrize("L", A3_LENGTHS)
-def test_attention3_lengths(ops, dt, L):
+def test_attention3_lengths(ops, guard, dt, L):
     B, heads = (3, 5) if L % 2 else (2, 12)
     E = heads * 64
     qkv = rnd(B * L, 3 * E, dt=dt, seed=230 + L)
-    out = torch.full((B * L, E), float("nan"), device="cuda", dtype=dt)
-    lse = torch.full((B, heads, L), float("nan"), device="cuda")
+    out = guard.out(B * L, E, dtype=dt)
+    lse = guard.out(B, heads, L)
     ops.attention_fwd(qkv, out, lse, B, L, heads, False)
     qd = qkv.double().requires_grad_(True)
     ref, ref_lse = ref_attention(qd, B, L, heads, False)
@@ -1357,18 +1485,19 @@ def test_attention3_lengths(ops, dt, L):
     check(lse, ref_lse.detach(), 2e-3 if dt == torch.bfloat16 else 3e-4, "lse")
     dout = rnd(B * L, E, dt=dt, seed=240 + L)
     ref.backward(dout.double())
-    dqkv = torch.full((B * L, 3 * E), float("nan"), device="cuda", dtype=dt)
-    delta = torch.full((B, heads, L), float("nan"), device="cuda")
+    dqkv = guard.out(B * L, 3 * E, dtype=dt)
+    delta = guard.out(B, heads, L)
     ops.attention_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, False)
     check(delta, (dout.double() * out.double()).reshape(B, L, heads, 64).sum(-1).permute(0, 2, 1), 1e-5, "delta")
     check(dqkv[:, :E], qd.grad[:, :E], 2 * t16, "dq")
     check(dqkv[:, E:2 * E], qd.grad[:, E:2 * E], 2 * t16, "dk")
     check(dqkv[:, 2 * E:], qd.grad[:, 2 * E:], 2 * t16, "dv")
+    guard.check()
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
 @pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
-def test_attention3_propagates_non_finite_inputs(ops, dt, bad):
+def test_attention3_propagates_non_finite_inputs(ops, guard, dt, bad):
     """attention3.hip is compiled with -fno-honor-nans (the row maxima), and the step's only divergence guard is the finite
     flag ce_loss raises from the logits: a NaN / Inf in q, k or v must therefore come out of the attention output (and a
     NaN / Inf in dO out of dq, dk, dv) and not be folded away by a max / select the compiler assumed NaN-free."""
@@ -1380,9 +1509,10 @@ def test_attention3_propagates_non_finite_inputs(ops, dt, bad):
         qkv = rnd(B * L, 3 * E, dt=dt, seed=250)
         col = {"q": 0, "k": E, "v": 2 * E}[which] + h * 64 + 7
         qkv[b * L + row, col] = bad
-        out = torch.zeros(B * L, E, device="cuda", dtype=dt)
-        lse = torch.zeros(B, heads, L, device="cuda")
+        out = guard.out(B * L, E, dtype=dt)
+        lse = guard.out(B, heads, L)
         ops.attention_fwd(qkv, out, lse, B, L, heads, False)
+        guard.check()
         o = out[rows, h * 64:(h + 1) * 64].float()
         hit = ~torch.isfinite(o).all(dim=1)
         if which == "q":
@@ -1398,23 +1528,24 @@ def test_attention3_propagates_non_finite_inputs(ops, dt, bad):
         out[rows, h * 64:(h + 1) * 64] = 0
         assert bool(torch.isfinite(out.float()).all())
     qkv = rnd(B * L, 3 * E, dt=dt, seed=251)
-    out = torch.zeros(B * L, E, device="cuda", dtype=dt)
-    lse = torch.zeros(B, heads, L, device="cuda")
+    out = guard.out(B * L, E, dtype=dt)
+    lse = guard.out(B, heads, L)
     ops.attention_fwd(qkv, out, lse, B, L, heads, False)
     dout = rnd(B * L, E, dt=dt, seed=252)
     dout[b * L + 11, h * 64 + 3] = bad
-    dqkv = torch.zeros(B * L, 3 * E, device="cuda", dtype=dt)
-    delta = torch.zeros(B, heads, L, device="cuda")
+    dqkv = guard.out(B * L, 3 * E, dtype=dt)
+    delta = guard.scratch(B, heads, L)
     ops.attention_bwd(qkv, out, dout, lse, delta, dqkv, B, L, heads, False)
     dq = dqkv[rows, h * 64:(h + 1) * 64].float()
     dk = dqkv[rows, E + h * 64:E + (h + 1) * 64].float()
     dv = dqkv[rows, 2 * E + h * 64:2 * E + (h + 1) * 64].float()
     assert not bool(torch.isfinite(dq[11]).all()), "dq of the poisoned row"
     assert not bool(torch.isfinite(dk).all()) and not bool(torch.isfinite(dv).all()), "dk / dv of the pair"
+    guard.check()
 
 
 @pytest.mark.parametrize("L", [197, 130])
-def test_attention3_running_maximum_and_rows(ops, L):
+def test_attention3_running_maximum_and_rows(ops, guard, L):
     """The second DMA half can raise a row's maximum (the rescale path): one key of the second half is made to dominate
     chosen queries, another row peaks in the first half; per-row comparison so that one wrong row cannot hide."""
     dt, B, heads = torch.bfloat16, 2, 3
@@ -1425,14 +1556,15 @@ def test_attention3_running_maximum_and_rows(ops, L):
     v[0, L - 2, 1, 1] = 3.0                                # ... against a key of the last tile: score 384 / 8
     v[1, 40, 0, 2] = -2.0
     v[1, 3, 1, 2] = -3.0                                   # query 40 of head 2 peaks at key 3 (first half)
-    out = torch.empty(B * L, E, device="cuda", dtype=dt)
-    lse = torch.empty(B, heads, L, device="cuda")
+    out = guard.out(B * L, E, dtype=dt)
+    lse = guard.out(B, heads, L)
     ops.attention_fwd(qkv, out, lse, B, L, heads, False)
     ref, ref_lse = ref_attention(qkv.double(), B, L, heads, False)
     err = (out.double() - ref).abs().reshape(B, L, heads, 64).amax(-1)
     assert float(err.max()) <= 1.2e-2 * float(ref.abs().max()), (float(err.max()), err.argmax())
     assert float((lse.double() - ref_lse).abs().max()) <= 2e-3 * float(ref_lse.abs().max())
     assert float(lse[0, 1, 5]) > 40.0                      # the spike really is the row maximum
+    guard.check()
 
 
 def test_attention3_is_the_kernel_that_runs_and_matches_the_second_generation():
@@ -1463,7 +1595,7 @@ def test_attention3_is_the_kernel_that_runs_and_matches_the_second_generation():
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
-def test_attention3_race_screen_bitwise_repeatable(ops, dt):
+def test_attention3_race_screen_bitwise_repeatable(ops, guard, dt):
     """attn3_* order their LDS-DMA by hand-counted s_waitcnt vmcnt(N) + raw s_barrier (no compiler-inserted waits): a read
     placed one phase early passes a reference check whenever the DMA happens to land first.  Screen: the bench shape (768
     blocks, three per CU) 30 times back to back, with a cache-flushing write between launches on every third run (the DMA then
@@ -1476,10 +1608,10 @@ def test_attention3_race_screen_bitwise_repeatable(ops, dt):
     flush = torch.empty(320 << 20, device="cuda", dtype=torch.uint8)
     first = None
     for it in range(30):
-        out = torch.full((B * L, E), float("nan"), device="cuda", dtype=dt)
-        lse = torch.full((B, heads, L), float("nan"), device="cuda")
-        dqkv = torch.full((B * L, 3 * E), float("nan"), device="cuda", dtype=dt)
-        delta = torch.full((B, heads, L), float("nan"), device="cuda")
+        out = guard.out(B * L, E, dtype=dt)
+        lse = guard.out(B, heads, L)
+        dqkv = guard.out(B * L, 3 * E, dtype=dt)
+        delta = guard.out(B, heads, L)
         if it % 3 == 1:
             flush.fill_(it)
         ops.attention_fwd(qkv, out, lse, B, L, heads, False)
@@ -1493,6 +1625,7 @@ def test_attention3_race_screen_bitwise_repeatable(ops, dt):
         else:
             for a, b, nm in zip(cur, first, ("out", "lse", "dqkv", "delta")):
                 assert torch.equal(a, b), f"run {it}: {nm} differs from run 0 in {int((a != b).sum())} elements"
+    guard.check()
 
 
 # ------------------------------- QuickGELU with the derivative as the saved tensor (ffm_gemm_args.gelu_deriv) ---
@@ -1509,7 +1642,7 @@ def _qgelu_grad64(x):
 @pytest.mark.parametrize("M,N,K,packed", [(333, 384, 256, False),        # 128 x 128 kernel
                                           (40, 512, 512, False),         # skinny kernel (text tower rows)
                                           (6304, 3072, 768, True)])      # panel kernel (16-bit: fragment-packed weights)
-def test_gemm_gelu_derivative_form(ops, dt, M, N, K, packed):
+def test_gemm_gelu_derivative_form(ops, guard, dt, M, N, K, packed):
     """FFM_EPI_GELU with gelu_deriv: `out` = quick_gelu'(x), `gelu_out` = quick_gelu(x), x the product as it would have been
     stored; FFM_EPI_DGELU with gelu_deriv: out = (a b^T) * aux.  Chained, the two launches give the classic pair's result:
     g W^T * quick_gelu'(pre) - bit-identical in fp32, to one 16-bit rounding of the derivative otherwise."""
@@ -1518,18 +1651,18 @@ def test_gemm_gelu_derivative_form(ops, dt, M, N, K, packed):
     a, w = rnd(M, K, dt=dt, seed=71), rnd(N, K, dt=dt, scale=K ** -0.5, seed=72)
     bias = rnd(N, seed=73)
     bp = ops.pack_b(w) if packed else None
-    d = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
-    act = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
-    pre = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
-    act0 = torch.full((M, N), float("nan"), device="cuda", dtype=dt)
+    d = guard.out(M, N, dtype=dt)
+    act = guard.out(M, N, dtype=dt)
+    pre = guard.out(M, N, dtype=dt)
+    act0 = guard.out(M, N, dtype=dt)
     kw = dict(bias=bias, b_packed=bp)
     if packed:                                   # the panel kernel's GELU epilogues are the FairLoRA ones: rank operand needed
         P = rnd(K, 8, scale=0.1, seed=74)
         rk = torch.zeros(16, K, device="cuda", dtype=dt)
         ops.PackPlan([(P, False, rk)], dt, "cuda").run()
         attr = torch.randint(0, 3, ((M + 196) // 197,), device="cuda", dtype=torch.int32)
-        mk = lambda: ops.RankOp(rk, rnd(3, 8, seed=75), attr, 197, 0.25, 0.7, t_out=torch.empty(M, 8, device="cuda"),
-                                ts_out=torch.empty(M, 8, device="cuda"))
+        mk = lambda: ops.RankOp(rk, rnd(3, 8, seed=75), attr, 197, 0.25, 0.7, t_out=guard.out(M, 8),
+                                ts_out=guard.out(M, 8))
         kw.update(lw=rnd(8, N, scale=0.1, seed=76))
         ops.gemm_nt(a, w, pre, gelu_out=act0, rankop=mk(), **kw)
         ops.gemm_nt(a, w, d, gelu_out=act, rankop=mk(), gelu_deriv=True, **kw)
@@ -1543,11 +1676,12 @@ def test_gemm_gelu_derivative_form(ops, dt, M, N, K, packed):
     check(act, _qgelu64(x), 1e-6 if dt == torch.float32 else tol(dt), "activation")
     # backward: g W * saved tensor, both forms
     g, wt = rnd(M, 64, dt=dt, seed=77), rnd(N, 64, dt=dt, scale=0.125, seed=78)
-    o0 = torch.empty(M, N, device="cuda", dtype=dt)
-    o1 = torch.empty(M, N, device="cuda", dtype=dt)
+    o0 = guard.out(M, N, dtype=dt)
+    o1 = guard.out(M, N, dtype=dt)
     ops.gemm_nt(g, wt, o0, dgelu_aux=pre)
     ops.gemm_nt(g, wt, o1, dgelu_aux=d, gelu_deriv=True)
     if dt == torch.float32:
         assert torch.equal(o0, o1), "fp32: the derivative form is the same arithmetic"
     check(o1, (g.double() @ wt.double().t()) * _qgelu_grad64(x), tol(dt) * 2, "dX with the saved derivative")
     check(o1, o0.double(), tol(dt) * 2, "derivative form vs classic form")
+    guard.check()
