@@ -731,6 +731,7 @@ extern "C" int ffm_lora_down(const void* x, int ldx, const float* P, int layout_
     const size_t es = dtype == FFM_BF16 ? 2 : 4;
     if (dtype != FFM_BF16 && dtype != FFM_F32) return FFM_EINVAL;
     if (((size_t)K * es) % 16 || ((size_t)ldx * es) % 16 || ((uintptr_t)x & 15)) return FFM_EINVAL;
+    if (ldx < K) return FFM_EINVAL;                                       // (rows would overlap: as ffm_gemm_nt / ffm_pack_b)
     hipStream_t s = (hipStream_t)stream;
     if (down_mfma_ok(M, K, r, dtype, layout_rk)) {
         hipLaunchKernelGGL(lora_down_mfma_kernel, dim3((M + LDM_ROWS - 1) / LDM_ROWS), dim3(LDM_WAVES * 64), 0, s, (const bf16_t*)x,
@@ -761,6 +762,7 @@ extern "C" int ffm_lora_grad_partial(const void* x, int ldx, const float* v, int
     const size_t es = dtype == FFM_BF16 ? 2 : 4;
     if (dtype != FFM_BF16 && dtype != FFM_F32) return FFM_EINVAL;
     if (((size_t)K * es) % 16 || ((size_t)ldx * es) % 16 || ((uintptr_t)x & 15)) return FFM_EINVAL;
+    if (ldx < K) return FFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == FFM_BF16 && K % LGM_COLS == 0) {             // matrix-core path (rank slots 16 at a time)
         for (int j0 = 0; j0 < r; j0 += 16) {
@@ -787,7 +789,7 @@ extern "C" int ffm_lora_grad_partial_ln(const void* x, int ldx, const float* v, 
                                         int dtype, void* stream) {
     if (!x || !v || !mean || !rstd || !gamma || !beta || !part || M <= 0 || K <= 0 || r <= 0) return FFM_EINVAL;
     if (dtype != FFM_BF16 || K % LGM_COLS || r > 16) return FFM_EUNSUP;
-    if (((size_t)ldx * 2) % 16 || ((uintptr_t)x & 15)) return FFM_EINVAL;
+    if (((size_t)ldx * 2) % 16 || ((uintptr_t)x & 15) || ldx < K) return FFM_EINVAL;
     const lgm_ln ln = {mean, rstd, gamma, beta};
     return launch_grad_mfma(x, ldx, v, M, K, r, part, r, 0, (hipStream_t)stream, &ln);
 }

@@ -462,6 +462,8 @@ int ffm_attention_bwd_lnstat(const void* qkv, const void* out, const void* dout,
  * The call writes exactly ffm_lora_down_blocks(M, K, r, dtype) partial rows of G * r floats (the count a reduction over
  * ds_part must use); ffm_lora_down_blocks_max(M_max, ...) bounds that count over every M <= M_max and is for sizing a
  * buffer once from the largest batch - never for summing.
+ * x: rows of K elements at a row stride of ldx elements; ldx >= K, and x and ldx * sizeof(element) multiples of 16 bytes
+ * (every row 16-byte aligned) - FFM_EINVAL otherwise.  Nothing between column K and ldx of a row is read.
  */
 int ffm_lora_down(const void* x, int ldx, const float* P, int layout_rk, const float* S,
                   const int32_t* attr, int M, int K, int r, int G, int rows_per_sample,
@@ -476,13 +478,14 @@ int ffm_lora_down_blocks_max(int M_max, int K, int r, int dtype); /* upper bound
  *   part[s][k][j] = sum_{m in split s} x[m][k] * v[m][j]
  * v = ts-style rows (already scaled by scaling * s_b).  part has
  * ffm_lora_grad_splits(M) * K * r floats.
+ * x as in ffm_lora_down: ldx >= K, rows 16-byte aligned (FFM_EINVAL otherwise).
  */
 int ffm_lora_grad_partial(const void* x, int ldx, const float* v, int M, int K, int r,
                           float* part, int dtype, void* stream);
 /* The same for x = LayerNorm(x_raw) that was never materialised (ln_2 folded into c_fc): x is the RAW rows,
  * mean / rstd [M] and gamma / beta [K] the LayerNorm, and with y = (x_raw - mean) rstd gamma + beta
  *   part[split][k][j] = gamma[k] (sum_m x_raw[m][k] rstd[m] v[m][j] - sum_m mean[m] rstd[m] v[m][j]) + beta[k] sum_m v[m][j].
- * bf16, K % 128 == 0, r <= 16. */
+ * bf16, K % 128 == 0, r <= 16; ldx >= K, rows 16-byte aligned (FFM_EINVAL otherwise). */
 int ffm_lora_grad_partial_ln(const void* x, int ldx, const float* v, const float* mean, const float* rstd,
                              const float* gamma, const float* beta, int M, int K, int r, float* part, int dtype,
                              void* stream);

@@ -19,6 +19,14 @@ are in front of the body, rows >= the body's row count behind it).  Where the co
 `check(defined=mask_or_index, of=buffer)` restricts the poison check of that buffer to the defined part; the caller states it
 from include/ffm_hip.h, never from what the kernel happened to write.
 
+`Guarded.window(rows, ld, col0, cols, dtype=...)` is the same for an operand whose row stride is wider than its rows: the
+body is [rows, ld], the tensor handed out is the strided view body[:, col0:col0 + cols], and everything of the body outside
+that view is FROZEN - `check()` also asserts that every such element still holds the poison bits, bit for bit, and names the
+(row, column) of the first that does not.  A store that spills from a window into the gap between its width and its row
+stride lands there, where neither a band nor a value comparison would see it.  `Guarded.window_in(rows, ld, col0, src)` is
+the input twin: `src` inside a [rows, ld] tensor of NaN, so that a load that strays out of the window and reaches an
+accumulator turns the result NaN.
+
 Every test file defines its own fixture around this class (see `guard_fixture`); the fixture fails at teardown when a
 registered buffer was never checked.
 """
@@ -61,8 +69,15 @@ class _Buf:
         self.ints[self.band:self.band + self.numel].fill_(self.poison_bits)
         self.flat = self.ints.view(dtype)                  # the whole backing buffer in the output's dtype
         self.body = self.flat[self.band:self.band + self.numel].view(self.shape)
+        self.view = self.body                              # what the caller holds (a window: a strided part of the body)
+        self.window = None                                 # (col0, cols): only these columns of the body may change
         self.defined = None
         self.checked = False
+
+    def set_window(self, col0, cols):
+        assert len(self.shape) == 2 and 0 <= col0 and cols > 0 and col0 + cols <= self.ld, "a window lies inside its rows"
+        self.window = (col0, cols)
+        self.view = self.body[:, col0:col0 + cols]
 
     def rowcol(self, linear):
         """(row, column) in the body's layout of the element `linear` elements after the body's first."""
@@ -70,6 +85,19 @@ class _Buf:
 
     def check(self):
         self.checked = True
+        left = self.ints[self.band:self.band + self.numel] == self.poison_bits
+        if self.window is not None:                        # (ahead of the bands: a spill reaches the gap of the next row first)
+            inside = torch.zeros(self.shape, dtype=torch.bool, device=self.ints.device)
+            inside[:, self.window[0]:self.window[0] + self.window[1]] = True
+            inside = inside.reshape(-1)
+            changed = ~left & ~inside
+            if bool(changed.any()):
+                first = int(changed.nonzero()[0])
+                r, c = self.rowcol(first)
+                lo, hi = self.window[0], self.window[0] + self.window[1]
+                raise AssertionError(f"'{self.name}' {list(self.shape)}, window columns [{lo}, {hi}): the frozen part outside the window "
+                                     f"changed: first at (row {r}, column {c}) of the body's layout, {int(changed.sum())} element(s) in all")
+            left = left & inside
         lead, trail = self.ints[:self.band], self.ints[self.band + self.numel:]
         for band, base, where in ((lead, -self.band, "in front of"), (trail, self.numel, "behind")):
             ref = torch.full_like(band, self.band_bits)
@@ -79,7 +107,6 @@ class _Buf:
                 r, c = self.rowcol(base + first)
                 raise AssertionError(f"guard band {where} '{self.name}' {list(self.shape)} changed: first at (row {r}, column {c}) "
                                      f"of the body's layout, {n} element(s) in all")
-        left = self.ints[self.band:self.band + self.numel] == self.poison_bits
         if self.defined is not None:
             left &= self.defined.reshape(-1)
         if bool(left.any()):
@@ -113,10 +140,27 @@ class Guarded:
         b.defined = torch.zeros(b.shape, dtype=torch.bool, device=self.device)
         return t
 
+    def window(self, rows, ld, col0, cols, dtype=torch.float32, name=None):
+        """The strided view body[:, col0:col0 + cols] of a poisoned [rows, ld] body between two guard bands.  The window is the
+        defined part; the rest of the body is frozen: `check()` fails when any element of it no longer holds the poison bits."""
+        b = _Buf(name or f"window{len(self.bufs)}", (rows, ld), dtype, self.device)
+        b.set_window(col0, cols)
+        self.bufs.append(b)
+        return b.view
+
+    def window_in(self, rows, ld, col0, src):
+        """An input behind a row stride: `src` [rows, cols] copied into columns col0.. of a [rows, ld] tensor of NaN, viewed as
+        that window.  Not registered: nothing is checked on it - a load outside the window shows as NaN in what it feeds."""
+        assert src.dim() == 2 and src.shape[0] == rows and col0 + src.shape[1] <= ld and src.dtype.is_floating_point
+        body = torch.full((rows, ld), float("nan"), dtype=src.dtype, device=self.device)
+        view = body[:, col0:col0 + src.shape[1]]
+        view.copy_(src)
+        return view
+
     def record(self, t):
-        """The bookkeeping of a body this object handed out (tests of the helper reach the backing buffer through it)."""
+        """The bookkeeping of a tensor this object handed out (tests of the helper reach the backing buffer through it)."""
         for b in self.bufs:
-            if b.body.data_ptr() == t.data_ptr() and b.body.shape == t.shape:
+            if b.view.data_ptr() == t.data_ptr() and b.view.shape == t.shape and b.view.stride() == t.stride():
                 return b
         raise KeyError("not a tensor from Guarded.out")
 
@@ -131,6 +175,7 @@ class Guarded:
                 assert len(self.bufs) == 1, "check(defined=...) needs of=<buffer> when several buffers are registered"
                 of = self.bufs[0].body
             b = self.record(of)
+            assert b.window is None, "a window is defined as a whole"
             if isinstance(defined, torch.Tensor) and defined.dtype == torch.bool:
                 mask = defined.to(self.device).expand(b.shape)
             else:
