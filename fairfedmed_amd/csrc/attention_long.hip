@@ -148,6 +148,25 @@ __device__ __forceinline__ float group4_max(float v) {   // lanes l, l^16, l^32,
     v = fmaxf(v, __shfl_xor(v, 16, 64));
     return fmaxf(v, __shfl_xor(v, 32, 64));
 }
+// IEEE half only (docs/experiments.md E15).  dS = P (dP - delta) / 8 goes to the matrix cores rounded to the storage type; it
+// is linear in the incoming gradient and carries P ~ 1 / L, so in half it is subnormal from |dO| ~ 2^-12 down (fp16 mode:
+// dO sits at 2^-10 rms at the default scale).  The wave's N fragments of one product step are scaled by the power of two that
+// puts their largest |.| into [2^4, 2^5) - returned; `inv` its inverse, which the product's fp32 result takes.  Exact both
+// ways; the exponent is clamped so that both factors are normal floats whatever the maximum is (0, infinite, subnormal).
+template <int N> __device__ __forceinline__ float wave_pow2(const f32x4* d, float& inv) {
+    float m = 0.f;
+#pragma unroll
+    for (int ff = 0; ff < N; ++ff)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(d[ff][e]));
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    int ex = m > 0.f ? ilogbf(m) : 0;
+    ex = ex < -100 ? -100 : ex > 100 ? 100 : ex;
+    inv = ldexpf(1.f, ex - 4);
+    return ldexpf(1.f, 4 - ex);
+}
+
 __device__ __forceinline__ float group4_sum(float v) {
     v += __shfl_xor(v, 16, 64);
     return v + __shfl_xor(v, 32, 64);
@@ -352,9 +371,26 @@ __global__ __launch_bounds__(NTH) void al_bwd_dq_kernel(const T* __restrict__ qk
                 }
                 d2[ff] = sa;
             }
+            if constexpr (std::is_same<T, f16_t>::value) {
+                float inv;
+                const float up = wave_pow2<FPK>(d2, inv);
+#pragma unroll
+                for (int ff = 0; ff < FPK; ++ff)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d2[ff][e] *= up;
+                const frag_t df = AL<T>::pack(d2);
+#pragma unroll
+                for (int fd = 0; fd < 4; ++fd) {
+                    f32x4 part = {0.f, 0.f, 0.f, 0.f};
+                    AL<T>::mma(part, AL<T>::tfrag(Kt, ts, fd * 16 + col, st, g), df);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dq[fd][e] += part[e] * inv;
+                }
+            } else {
             const frag_t df = AL<T>::pack(d2);
 #pragma unroll
             for (int fd = 0; fd < 4; ++fd) AL<T>::mma(dq[fd], AL<T>::tfrag(Kt, ts, fd * 16 + col, st, g), df);
+            }
         }
     }
     if (q < L) {
@@ -460,11 +496,29 @@ __global__ __launch_bounds__(NTH) void al_bwd_dkv_kernel(const T* __restrict__ q
                 d2[ff] = pa;
             }
             const frag_t pf = AL<T>::pack(p2);
+            if constexpr (std::is_same<T, f16_t>::value) {
+                float inv;
+                const float up = wave_pow2<FPK>(d2, inv);
+#pragma unroll
+                for (int ff = 0; ff < FPK; ++ff)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d2[ff][e] *= up;
+                const frag_t df = AL<T>::pack(d2);
+#pragma unroll
+                for (int fd = 0; fd < 4; ++fd) {
+                    AL<T>::mma(dv[fd], AL<T>::tfrag(dOt, ts, fd * 16 + col, st, g), pf);
+                    f32x4 part = {0.f, 0.f, 0.f, 0.f};
+                    AL<T>::mma(part, AL<T>::tfrag(Qt, ts, fd * 16 + col, st, g), df);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dk[fd][e] += part[e] * inv;
+                }
+            } else {
             const frag_t df = AL<T>::pack(d2);
 #pragma unroll
             for (int fd = 0; fd < 4; ++fd) {
                 AL<T>::mma(dv[fd], AL<T>::tfrag(dOt, ts, fd * 16 + col, st, g), pf);
                 AL<T>::mma(dk[fd], AL<T>::tfrag(Qt, ts, fd * 16 + col, st, g), df);
+            }
             }
         }
     }

@@ -968,7 +968,10 @@ __attribute__((amdgpu_waves_per_eu(panel_waves_per_eu<MF, NF, RK, PWV>(), panel_
     // of one row per lane: every lane drops its 16-bit chunk (the rows as stored / the activation recomputed from the
     // pre-activation chunk it holds anyway) into a [32][WN] image over the part of the wave's stage that has been read
     // already, and ds_read_b64_tr_b16 hands the image back transposed (the reduction kernel's own recipe, lora.hip).
-    // V enters as a bf16 hi + lo pair (fp32-level accuracy in v, as there).  No VMEM in here: the counted waits stand.
+    // V enters as a 16-bit hi + lo pair: fp32-level accuracy in v in bf16; in the half twin the pair is NOT scaled here
+    // (lg_split), so it loses a bit per binade v sinks below ~2^-4 - measured, the us operand of part_a keeps the 2e-3 of
+    // its test down to an rms of 2^-15.5 (dL/dy at 2^-14; 6e-4 there, 1.7e-4 at 2^-12), below the 2^-13.1 the fp16 mode
+    // reaches at the scale 256 and batch 64 (docs/experiments.md E15).  No VMEM in here: the counted waits stand.
     // Both images are written INSIDE the chunk loop (the activation shares the sigmoid of the derivative there: recomputed
     // behind the loop its exp + rcp cost 12 us per launch), interleaved row by row - image row R of both at 2 TROW R, 16
     // bytes short of the stage's row pitch - so that what iteration i writes (rows it has just read) ends below the first

@@ -455,7 +455,9 @@ int launch_grad(const void* x, int ldx, const float* v, int M, int K, int r, flo
 // is the product V^T [16 x rows] . X [rows x K] with the ROW index contracted, i.e. X is needed column-major.
 // One wave per block owns a 128-row x 128-column tile of X: 32 LDS-DMA pieces (4 rows x 256 B each) land it
 // row-major in LDS (coalesced from HBM), ds_read_b64_tr_b16 hands it to the MFMA B operand transposed, and v goes
-// into the A operand as a bf16 hi + lo pair (two MFMAs), so the result keeps fp32-level accuracy in v.
+// into the A operand as a 16-bit hi + lo pair (two MFMAs), so the result keeps fp32-level accuracy in v: 3.8e-6 of the
+// result's scale in bf16 at any magnitude of v; in the half twin (-DFFM_TWIN_F16) only because the tile's v is scaled by a
+// power of two first - unscaled, the pair of halves crossed 2e-4 at |v| ~ 2^-13 (tests/test_grad_range_gpu.py).
 // 32 KiB of LDS per block -> 5 blocks per CU: the whole 6304 x 3072 operand (24 x 50 = 1200 tiles) is in flight at
 // once and the kernel runs at the HBM rate instead of the load latency of a VALU loop.
 // LDS image: 256-byte rows, 16-byte chunk ch of row r at 256 r + 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))) --
@@ -512,6 +514,47 @@ __global__ __launch_bounds__(64) void lora_grad_mfma_kernel(const bf16_t* __rest
     const int j = lane & 15, kg = lane >> 4;
     bf16x8 ahi[4], alo[4];
     float s1 = 0.f, s2 = 0.f;                                  // LN: sum_m mean rstd v, sum_m v (this lane's rows)
+#ifdef FFM_TWIN_F16
+    // IEEE half: a pair of halves holds 22 bits only while lo stays above half's subnormal spacing 2^-24 - for |v| <~ 2^-4
+    // every binade v sinks costs the pair a bit, and v is a GRADIENT here (us, 2^-9 rms in a ViT-B/16 step at the default
+    // scale, 2^-14 at the scale 256).  So the block's v tile goes in times an exact power of two that puts its largest
+    // |v| into [2^4, 2^5), and the accumulators take the inverse at the store (docs/experiments.md E15).
+    float vall[4][8];
+    float amax = 0.f;
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int gm = m0 + rb * 32 + kg * 8 + t;
+            float vv = (j < r && gm < M) ? v[(size_t)gm * rs + j0 + j] : 0.f;
+            if constexpr (LN) {
+                const int gc = gm < M ? gm : M - 1;
+                const float rsd = ln.rstd[gc];
+                s2 += vv;
+                vv *= rsd;
+                s1 += ln.mean[gc] * vv;
+            }
+            vall[rb][t] = vv;
+            amax = fmaxf(amax, fabsf(vv));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    // amax = m 2^ex, 1 <= m < 2 (ex clamped to the normal floats: an infinite or subnormal maximum scales by a finite factor)
+    int ex = amax > 0.f ? ilogbf(amax) : 0;
+    ex = ex < -100 ? -100 : ex > 100 ? 100 : ex;
+    const float v_up = ldexpf(1.f, 4 - ex), v_down = ldexpf(1.f, ex - 4);
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float vs = vall[rb][t] * v_up;
+            const bf16_t h = (bf16_t)vs;
+            ahi[rb][t] = h;
+            alo[rb][t] = (bf16_t)(vs - (float)h);
+        }
+    }
+#else
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
         float vv[8];
@@ -534,6 +577,7 @@ __global__ __launch_bounds__(64) void lora_grad_mfma_kernel(const bf16_t* __rest
             alo[rb][t] = (bf16_t)(vv[t] - (float)h);
         }
     }
+#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                              // single wave: orders the DMA writes before the reads
 
@@ -593,7 +637,12 @@ __global__ __launch_bounds__(64) void lora_grad_mfma_kernel(const bf16_t* __rest
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int jj = 4 * kg + e;
-            if (jj < r) dst[jj] = LN ? gk * (acc[cf][e] - c1[e]) + bk * c2[e] : acc[cf][e];
+#ifdef FFM_TWIN_F16
+            const float a = acc[cf][e] * v_down;                  // (the tile's power of two leaves again: exact)
+#else
+            const float a = acc[cf][e];
+#endif
+            if (jj < r) dst[jj] = LN ? gk * (a - c1[e]) + bk * c2[e] : a;
         }
     }
 }

@@ -22,6 +22,13 @@ def rel(got, ref):
     return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
+def hold(got, ref, t, what):
+    """The backward assertions of the *_case bodies: max error / max |ref| strictly below t.  (A function of its own so that
+    tests/test_grad_range_gpu.py can record the same comparison over a sweep of gradient magnitudes.)"""
+    e = rel(got, ref)
+    assert e < t, f"{what}: max err / scale = {e:.3e} >= {t:.1e}"
+
+
 def rnd(*shape, dt=torch.float32, scale=1.0, seed=0):
     g = torch.Generator(device="cuda").manual_seed(seed + sum(shape))
     return (torch.randn(*shape, device="cuda", generator=g) * scale).to(dt)
@@ -53,7 +60,7 @@ def test_conv3x3_forward_and_input_gradient(ops, guard, dt, B, H, C, Co, stride)
     im2col_case(ops, guard, dt, B, H, H, C, Co, stride)
 
 
-def im2col_case(ops, guard, dt, B, H, W, C, Co, stride):
+def im2col_case(ops, guard, dt, B, H, W, C, Co, stride, gscale=1.0):
     x = rnd(B, C, H, W, dt=dt, seed=1)
     w = rnd(Co, C, 3, 3, dt=dt, scale=(9 * C) ** -0.5, seed=2)
     Ho, Wo = ops.conv_out(H, stride), ops.conv_out(W, stride)
@@ -70,7 +77,7 @@ def im2col_case(ops, guard, dt, B, H, W, C, Co, stride):
     # the K padding of cols is defined as zero (include/ffm_hip.h), so the whole body counts as written
     assert float(cols[:, 9 * C:].float().abs().max() if Kp > 9 * C else 0.0) == 0.0
     # dX: dcols = dY W, then the gather
-    dy = rnd(B, Co, Ho, Wo, dt=dt, seed=3)
+    dy = rnd(B, Co, Ho, Wo, dt=dt, scale=gscale, seed=3)                # the gradient operand
     wt = torch.zeros(Kp, Co, device="cuda", dtype=dt)
     wt[:9 * C] = wk[:, :9 * C].t()
     dcols = guard.out(B * Ho * Wo, Kp, dtype=dt)
@@ -79,7 +86,7 @@ def im2col_case(ops, guard, dt, B, H, W, C, Co, stride):
     ops.col2im3x3(dcols, dx, B, H, W, stride)
     xr = x.double().requires_grad_()
     F.conv2d(xr, w.double(), stride=stride, padding=1).backward(dy.double())
-    assert rel(nchw(dx, B, H, W), xr.grad) < tol(dt) * 2
+    hold(nchw(dx, B, H, W), xr.grad, tol(dt) * 2, "col2im3x3: dx")
     guard.check()
 
 
@@ -118,7 +125,7 @@ def test_batchnorm_train_forward_backward_and_eval(ops, guard, dt, rows, C, relu
     batchnorm_case(ops, guard, dt, rows, C, relu, with_res)
 
 
-def batchnorm_case(ops, guard, dt, rows, C, relu, with_res):
+def batchnorm_case(ops, guard, dt, rows, C, relu, with_res, gscale=1.0):
     x = rnd(rows, C, dt=dt, seed=7) * 1.5 + 0.3
     gamma, beta = 1 + 0.1 * rnd(C, seed=8), 0.1 * rnd(C, seed=9)
     rm, rv = 0.05 * rnd(C, seed=10), 1 + 0.1 * rnd(C, seed=11).abs()
@@ -139,14 +146,16 @@ def batchnorm_case(ops, guard, dt, rows, C, relu, with_res):
     assert rel(y, ref.detach()) < tol(dt)
     assert rel(rm1, rmr) < 1e-5 and rel(rv1, rvr) < 1e-5
     # backward (through the ReLU mask when there is one)
-    dy = rnd(rows, C, dt=dt, seed=13)
+    dy = rnd(rows, C, dt=dt, scale=gscale, seed=13)                     # the gradient operand
     ref.backward(dy.double())
     k12, dg, db = guard.scratch(2 * C), guard.out(C), guard.out(C)
     dx = guard.like(x)
     gout = guard.like(x)
     ops.bn_bwd(dy, y if relu else None, x, gamma, mean, rstd, part, k12, dg, db, dx, g_out=gout)
     t = tol(dt) * (3 if dt == torch.float32 else 1)
-    assert rel(dx, xr.grad) < t and rel(dg, gr.grad) < t and rel(db, br.grad) < t
+    hold(dx, xr.grad, t, "bn_bwd: dx")
+    hold(dg, gr.grad, t, "bn_bwd: dgamma")
+    hold(db, br.grad, t, "bn_bwd: dbeta")
     assert torch.equal(gout, dy * (y > 0) if relu else dy)        # g_out: the ReLU-masked gradient (ffm_relu_bwd's result)
     # eval mode: running statistics, nothing updated
     rm2, rv2 = rm.clone(), rv.clone()
@@ -161,24 +170,25 @@ def test_avgpool_add_relu_and_attnpool_tokens(ops, guard, dt):
     pool_add_relu_tokens_case(ops, guard, dt, 4)
 
 
-def pool_add_relu_tokens_case(ops, guard, dt, HW):
+def pool_add_relu_tokens_case(ops, guard, dt, HW, gscale=1.0):
     B, H, C = 3, 8, 64
     x = rnd(B, C, H, H, dt=dt, seed=20)
     out = guard.out(B * 16, C, dtype=dt)
     ops.avgpool2(nhwc(x), out, B, H, H)
     assert rel(nchw(out, B, 4, 4), F.avg_pool2d(x.double(), 2)) < tol(dt)
-    dp = rnd(B * 16, C, dt=dt, seed=21)
+    dp = rnd(B * 16, C, dt=dt, scale=gscale, seed=21)                   # the gradient operands: dp, ffm_relu_bwd's g, dt_
     dx = guard.out(B * H * H, C, dtype=dt)
     ops.avgpool2(dp, dx, B, H, H, backward=True)
     xr = x.double().requires_grad_()
     F.avg_pool2d(xr, 2).backward(nchw(dp, B, 4, 4).double())
-    assert rel(nchw(dx, B, H, H), xr.grad) < tol(dt)
+    hold(nchw(dx, B, H, H), xr.grad, tol(dt), "avgpool2 backward")
     a, b = rnd(640, C, dt=dt, seed=22), rnd(640, C, dt=dt, seed=23)
     o = guard.like(a)
     ops.add(a, b, o)
     assert rel(o, a.double() + b.double()) < tol(dt)
-    ops.relu_bwd(a, b, o)
-    assert rel(o, a.double() * (b.double() > 0)) < 1e-7
+    ga = rnd(640, C, dt=dt, scale=gscale, seed=22)
+    ops.relu_bwd(ga, b, o)
+    hold(o, ga.double() * (b.double() > 0), 1e-7, "relu_bwd")
     # attention-pool tokens
     E = 128
     feat = rnd(B * HW, E, dt=dt, seed=24)
@@ -188,11 +198,11 @@ def pool_add_relu_tokens_case(ops, guard, dt, HW):
     fr = feat.double().reshape(B, HW, E).requires_grad_()
     ref = torch.cat([fr.mean(1, keepdim=True), fr], 1) + pos.double()
     assert rel(tok.reshape(B, HW + 1, E), ref.detach()) < tol(dt)
-    dt_ = rnd(B * (HW + 1), E, dt=dt, seed=26)
+    dt_ = rnd(B * (HW + 1), E, dt=dt, scale=gscale, seed=26)
     ref.backward(dt_.double().reshape(B, HW + 1, E))
     df = guard.like(feat)
     ops.attnpool_tokens(dt_, None, df, B, HW, backward=True)
-    assert rel(df.reshape(B, HW, E), fr.grad) < tol(dt)
+    hold(df.reshape(B, HW, E), fr.grad, tol(dt), "attnpool_tokens backward")
     guard.check()
 
 
@@ -220,7 +230,7 @@ def test_implicit_gemm_conv3x3_forward_and_input_gradient(ops, guard, dt, B, H, 
     implicit_conv_case(ops, guard, dt, B, H, W, C, Co)
 
 
-def implicit_conv_case(ops, guard, dt, B, H, W, C, Co):
+def implicit_conv_case(ops, guard, dt, B, H, W, C, Co, gscale=1.0):
     """ffm_conv3x3_nhwc: the patches are never materialised; forward and (with the re-ordered weight) the input
     gradient against F.conv2d and its autograd, incl. non-square maps, tile-ragged pixel counts and padded K."""
     kq = 64 if dt != torch.float32 else 32
@@ -237,11 +247,11 @@ def implicit_conv_case(ops, guard, dt, B, H, W, C, Co):
     y2 = guard.like(y)
     ops.conv3x3(nhwc(x), _rows_fwd(w, rup(9 * C)).to(dt), y2, B, H, W, zeros, scratch)
     assert rel(nchw(y2.float(), B, H, W), ref.detach()) < tol(dt)
-    g = rnd(B, Co, H, W, dt=dt, seed=3)
+    g = rnd(B, Co, H, W, dt=dt, scale=gscale, seed=3)                   # the gradient operand
     ref.backward(g.float())
     dx = guard.out(B * H * W, C, dtype=dt)
     ops.conv3x3(nhwc(g), _rows_bwd(w, rup(9 * Co)).to(dt), dx, B, H, W, zeros, scratch)
-    assert rel(nchw(dx.float(), B, H, W), xr.grad) < tol(dt)
+    hold(nchw(dx.float(), B, H, W), xr.grad, tol(dt), "conv3x3 input gradient")
     guard.check()
 
 

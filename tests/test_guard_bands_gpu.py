@@ -391,18 +391,19 @@ def panel_lnin_rank_case(ops, guard, kind, M, dt):
     guard.check()
 
 
-def panel_plain_lnb_apply_case(ops, guard, M, dt):
+def panel_plain_lnb_apply_case(ops, guard, M, dt, gscale=1.0):
     """FFM_EPI_LNB_APPLY without rank terms (the dX product of the in-projection applying ln_1's backward): out =
     rstd (gamma g_h - c1 / K - xhat c2 / K) + res with g_h = a b^T, c1 / c2 the sums over the np partial rows of `part`
-    (include/ffm_hip.h) - float64 on the same operands at the bound of the folded-backward tests, tol(dt)."""
+    (include/ffm_hip.h) - float64 on the same operands at the bound of the folded-backward tests, tol(dt).
+    gscale multiplies the gradient operands: g, res and the row sums of `part` (tests/test_grad_range_gpu.py)."""
     E, np_ = 768, 4
     assert ops.gemm_tile_shape(M, E, 3 * E, L.EPI_LNB_APPLY, 0, dt, True)[0] >= 0, "shape does not select the panel kernel"
-    g, Wt = rnd(M, 3 * E, dt=dt, seed=601), rnd(E, 3 * E, dt=dt, scale=(3 * E) ** -0.5, seed=602)
+    g, Wt = rnd(M, 3 * E, dt=dt, scale=gscale, seed=601), rnd(E, 3 * E, dt=dt, scale=(3 * E) ** -0.5, seed=602)
     x = rnd(M, E, dt=dt, seed=603) * 1.5 + 0.3
-    gamma, res = 1 + 0.1 * rnd(E, seed=604), rnd(M, E, dt=dt, seed=605)
+    gamma, res = 1 + 0.1 * rnd(E, seed=604), rnd(M, E, dt=dt, scale=gscale, seed=605)
     xd = x.double()
     mu, rs = xd.mean(1), 1 / torch.sqrt(xd.var(1, unbiased=False) + 1e-5)
-    part = rnd(np_, M, 2, seed=606)
+    part = rnd(np_, M, 2, scale=gscale, seed=606)
     out = guard.out(M, E, dtype=dt, name="out")
     ops.gemm_nt(g, Wt, out, b_packed=ops.pack_b(Wt),
                 lnb_apply=ops.LnBwdApply(part, np_, x, gamma, mu.float().contiguous(), rs.float().contiguous(), None, res))
