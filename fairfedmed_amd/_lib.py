@@ -157,6 +157,7 @@ SIGNATURES = {
     "ffm_dp_privatise": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _i64, _i32, _i32, _i32, _vp, _vp],
     "ffm_dp_noise": [_vp, _i64, _f32, _i64, _i32, _i32, _vp],
     "ffm_dp_philox": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp],
+    "ffm_drift_correct": [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp],
     "ffm_cast_f32_to": [_vp, _vp, _i64, _i32, _vp],
     "ffm_cast_to_f32": [_vp, _vp, _i64, _i32, _vp],
     "ffm_transpose_cast": [_vp, _vp, _i32, _i32, _i32, _vp],

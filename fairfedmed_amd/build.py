@@ -25,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libffm_hip.so")
-SOURCES = ["gemm.hip", "gemm_panel.hip", "gemm_panel_rk.hip", "gemm_panel_rk2.hip", "gemm_panel_rk3.hip", "gemm_skinny.hip", "rowwise.hip", "lora.hip", "head.hip", "head_ot.hip", "optim.hip", "dp.hip", "attention.hip", "attention3.hip", "attention_long.hip", "slice3d.hip", "conv.hip", "evalmetrics.hip", "evalsort.hip", "evalboot.hip", "transport.hip", "resize.hip", "augment.hip", "text.hip", "switches.hip"]
+SOURCES = ["gemm.hip", "gemm_panel.hip", "gemm_panel_rk.hip", "gemm_panel_rk2.hip", "gemm_panel_rk3.hip", "gemm_skinny.hip", "rowwise.hip", "lora.hip", "head.hip", "head_ot.hip", "optim.hip", "dp.hip", "drift.hip", "attention.hip", "attention3.hip", "attention_long.hip", "slice3d.hip", "conv.hip", "evalmetrics.hip", "evalsort.hip", "evalboot.hip", "transport.hip", "resize.hip", "augment.hip", "text.hip", "switches.hip"]
 # files with 16-bit kernels behind a `dtype` argument (attention3.hip and attention_long.hip are templated on the storage types and need no
 # twin; switches.hip has no kernels: the one switch table, csrc/switches.h, that the main objects and the twins both read)
 TWIN_SOURCES = ["gemm.hip", "gemm_panel.hip", "gemm_panel_rk.hip", "gemm_panel_rk2.hip", "gemm_panel_rk3.hip", "gemm_skinny.hip", "rowwise.hip", "lora.hip", "head.hip", "head_ot.hip", "attention.hip", "slice3d.hip", "conv.hip"]

@@ -643,6 +643,7 @@ class ClipEngine:
         self._counts_buf = None                       # enable_step_counts()
         # set_fairness(): lambda and with_grad of the loss's group-confidence-gap term; {cls, F} and {m_g, n_g} per group
         self._fair_lam, self._fair_grad, self._fair_step = 0.0, False, False
+        self._drift = None                            # set_drift(): a drift.DriftCorrector applied behind every backward pass
         self.loss_terms = torch.zeros(2, device=dev, dtype=f32)
         self.group_conf = torch.zeros(ops.MAX_GROUPS, 2, device=dev, dtype=f32)
         self.tbar_buf = torch.zeros(cfg.n_cls, v.out_dim, device=dev, dtype=f32)
@@ -1229,6 +1230,8 @@ class ClipEngine:
             self._after_plan(b, S)
             if self.scale_state is not None:
                 ops.unscale_check(self.params.grad, self.scale_state)
+            if self._drift is not None:                 # set_drift: on true-scale gradients, outside the recorded plan
+                self._drift.apply(self.params.grad, self.params.flat, self.scale_state)
         out = {"loss": self.loss, "logits": self.logits[:b], "prob": self.prob[:b], "finite": self.finite}
         if self._counts_buf is not None:
             out["counts"] = self._counts_buf          # ffm_eval_counts of (prob, label): rows {unknown, all}
@@ -1307,6 +1310,16 @@ class ClipEngine:
         if (lam, with_grad) != (self._fair_lam, self._fair_grad):
             self._fair_lam, self._fair_grad = lam, with_grad
             self.step_plans.clear()
+
+    def set_drift(self, corrector) -> None:
+        """Client-drift correction of the local step (fairfedmed_amd.drift.DriftCorrector; an
+        extension beyond the reference): with a corrector, every forward_backward ends in one more launch - ffm_drift_correct
+        on params.grad, behind the plan and (fp16) behind unscale_check, so it sees true-scale gradients and is skipped with
+        an overflowed step - in front of whichever optimizer step follows; None (the default) launches nothing.  The launch
+        is not part of the recorded plans, so they stay as they are.  A captured step (capture_train_step) contains the
+        launch if it was captured after this call, with the corrector's buffers by address and FedProx's mu baked in: call
+        this BEFORE the capture, as set_fairness.  The reported loss stays the task loss."""
+        self._drift = corrector
 
     def _fair_groups(self) -> int:
         """Groups the loss's term looks for: the adapters' for FairLoRA (an attribute beyond them could not pass through
@@ -1631,6 +1644,8 @@ class GraphedStep:
         live = [p.flat, p.momentum, p.grad, eng.finite] + ([eng.scale_state] if eng.scale_state is not None else [])
         if self.spec is not None:                     # every state row and the device-resident step count / powers
             live = [p.flat, p.optim_state, p.grad, eng.finite, eng.optim_desc_dev(self.spec, lr)] + live[4:]
+        if eng._drift is not None:                    # set_drift: the running gradient sum and its step count
+            live = live + eng._drift.live()
         keep, steps = [t.clone() for t in live], p.steps
 
         def restore():

@@ -186,14 +186,16 @@ class FedAvgAggregator:
         self._grouped = self._grouped or n_client_by_attr is not None
 
     @torch.no_grad()
-    def finish(self, epoch: int, max_epoch: int, grouped: Optional[bool] = None) -> Tensor:
+    def finish(self, epoch: int, max_epoch: int, grouped: Optional[bool] = None, reduce: bool = True) -> Tensor:
         """All ranks call this once per round; returns the new global weights (``global_prev``, updated in place;
         utils/fed_utils.py:88-98: w = (1-b)*avg + b*w_g with b = beta * epoch / max_epoch).  ``grouped``: whether the
         per-attribute counts were in play (the reference's guard on shared_half_s) - by default what ``add`` saw; a rank
-        without a client of its own passes it explicitly."""
+        without a client of its own passes it explicitly.  ``reduce=False``: every rank has added EVERY participant itself
+        (``run_fedotplora_ranks`` with a drift correction, which exchanges the clients' buffers first so that the sum has one
+        order whatever the world size), so there is nothing to all-reduce; the passes behind it are the same."""
         if self._added == 0:
             self.buf.zero_()
-        if dist.is_available() and dist.is_initialized():
+        if reduce and dist.is_available() and dist.is_initialized():
             dist.all_reduce(self.buf, op=dist.ReduceOp.SUM, group=self.group)
         beta_decay = self.beta * (epoch / max(max_epoch, 1))
         use_half = self.shared_half_s and (self._grouped if grouped is None else grouped) and self.s_offsets.numel() > 0

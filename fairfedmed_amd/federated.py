@@ -55,6 +55,11 @@ class FedArgs:
     dp_noise: float = 0.0
     dp_seed: Optional[int] = None
     dp_delta: float = 1e-5
+    # Client-drift correction in the local step (drift.py; an extension beyond the reference's
+    # FedOTPLoRA branch).  drift: none | fedprox | scaffold; mu: the weight of FedProx's proximal term (the reference's --mu
+    # and its default), read with drift == "fedprox" only.
+    drift: str = "none"
+    mu: float = 0.5
 
 
 def dp_config(args: FedArgs, trainer=None):
@@ -74,6 +79,33 @@ def dp_config(args: FedArgs, trainer=None):
                          "the privacy bound would not hold; use a ViT tower or run without dp_clip")
     seed = args.dp_seed if args.dp_seed is not None else (args.seed if args.seed is not None else 0)
     return DPCfg(clip=args.dp_clip, noise_multiplier=args.dp_noise, seed=int(seed), delta=args.dp_delta)
+
+
+def drift_corrector(args: FedArgs, trainer, users: int):
+    """The DriftCorrector of a run over the engine's flat trainable buffer, or None with --drift none."""
+    from .drift import NAMES, DriftCfg, DriftCorrector
+    if args.drift not in NAMES:
+        raise ValueError(f"drift must be one of {NAMES}, got {args.drift!r}")
+    if args.drift == "none":
+        return None
+    eng = getattr(trainer, "engine", None)
+    if eng is None or not hasattr(eng, "set_drift") or not hasattr(eng, "params"):
+        raise ValueError(f"drift {args.drift!r} needs a trainer whose engine has set_drift (the correction is applied to its "
+                         "flat gradient buffer in front of the optimizer step)")
+    if len(args.idxs_users_train) > 0:
+        raise ValueError(f"drift {args.drift!r} with idxs_users_train {list(args.idxs_users_train)}: the personalised tensors of "
+                         "those clients are never averaged, so a pull towards the round's start or a control variate on them "
+                         "has no meaning; run without idxs_users_train or with drift none")
+    if args.drift == "scaffold" and args.dp_clip:
+        raise ValueError("drift 'scaffold' with dp_clip > 0: the control variates are a second quantity every client releases, "
+                         "with no clip and no noise on it, so the privacy bound would not hold; use drift fedprox or none")
+    return DriftCorrector(eng.params.flat, users, DriftCfg(args.drift, float(args.mu) if args.drift == "fedprox" else 0.0))
+
+
+def _drift_log(hist, info: dict, epoch: int, log) -> None:
+    hist.setdefault("drift", []).append(info)
+    if info["steps"]:
+        log(f"round {epoch}: drift |c| {info['c_norm']:.4g}  local steps " + " ".join(f"{c}:{k}" for c, k in info["steps"].items()))
 
 
 def _dp_log(hist, dp, stats: Dict[int, tuple], epoch: int, log) -> None:
@@ -210,8 +242,11 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
         np.random.seed(args.seed)
     n_client, by_attr = _counts(trainer, attribute, users)
     dp = dp_config(args, trainer)
+    corr = drift_corrector(args, trainer, users)
     boot = _bootstrap_on(trainer)
     trainer.fed_before_train()
+    if corr is not None:
+        trainer.engine.set_drift(corr)
     # Only the trainable tensors travel: the reference averages the whole state_dict, but frozen tensors are
     # identical on every client, so their weighted mean is the tensor itself up to one rounding per round
     # (SURVEY §5 quirk 10); leaving them out also keeps the engine's packed copies of the frozen weights valid.
@@ -243,7 +278,11 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
             agg.begin(round=epoch)
         for idx in idxs_users:
             trainer.model.load_state_dict(global_weights if epoch == 0 else local_weights_per[idx], strict=False)
+            if corr is not None:
+                corr.begin_client(idx)
             trainer.train(idx=idx, global_epoch=epoch, is_fed=True, is_last_client=idx == idxs_users[-1])
+            if corr is not None:
+                corr.end_client(idx)
             lw = snap()
             local_ctx[idx] = copy.deepcopy(lw["prompt_learner.ctx"][args.avg_prompt:args.num_prompt])
             local_s[idx] = copy.deepcopy({k: v for k, v in lw.items() if "lora_S" in k})
@@ -257,6 +296,8 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
             g = agg.finish(epoch, args.round, grouped=by_attr is not None)
             global_weights = {k: g[off:off + int(np.prod(shp))].view(shp).clone() for k, (off, shp) in params.offsets.items()}
             _dp_log(hist, dp, agg.dp_stats, epoch, log)
+        if corr is not None:
+            _drift_log(hist, corr.finish_round(idxs_users), epoch, log)
         all_users = list(args.idxs_users_test) if len(args.idxs_users_test) > 0 else list(range(users))
         results, ci, full = [], {}, {}
         for idx in all_users:
@@ -275,6 +316,8 @@ def run_fedotplora(trainer, args: FedArgs, attribute: Optional[str] = None, log=
         hist["time"].append(time.time() - start)
         log(f"Global test acc: {hist['acc'][-1]}  macro_f1: {hist['f1'][-1]}"
             + (f"  auc: {hist['auc'][-1]}" if hist["auc"] else ""))
+    if corr is not None:
+        trainer.engine.set_drift(None)
     trainer.fed_after_train()
     hist["global_weights"] = global_weights
     hist["local_weights_per"] = local_weights_per
@@ -302,8 +345,16 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
     flat, offsets = params.flat, params.offsets
     lo = trainer.engine.cfg.lora
     dp = dp_config(args, trainer)
+    corr = drift_corrector(args, trainer, users)
     boot = _bootstrap_on(trainer)
     trainer.fed_before_train()
+    if corr is not None:
+        trainer.engine.set_drift(corr)
+    # With a drift correction the round's sum must not depend on how the clients were dealt to the ranks (the control variates
+    # feed every later step, so one bit in the global weights reaches everything behind it): the trained buffers are exchanged
+    # first - a zero-padded [users, n] all-reduce, exact because one rank contributes each row - and every rank then adds all
+    # participants in the round's order, which is the one-process driver's order.
+    trained = torch.zeros(users, flat.numel(), device=flat.device) if corr is not None else None
     agg = FedAvgAggregator(flat, offsets, lo.num_groups, lo.rank, shared_half_s=args.shared_half_s, beta=0.999, dp=dp)
     global_flat = agg.global_prev                                    # updated in place by agg.finish()
     per_client = {i: global_flat.clone() for i in range(users)}      # personalised flat buffers (this rank's view)
@@ -344,10 +395,17 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
                     eng.load_buffers_flat(global_buf if epoch == 0 else per_client_buf[idx])
                 if can_position:
                     trainer.set_lr_epoch(sched_pos + j * per_client_epochs)
+                if corr is not None:
+                    corr.begin_client(idx)
                 trainer.train(idx=idx, global_epoch=epoch, is_fed=True, is_last_client=idx == idxs_users[-1])
+                if corr is not None:
+                    corr.end_client(idx)
                 if args.idxs_users_train:
                     local_after[idx] = flat.detach().clone()
-                agg.add(flat, idx, idxs_users, n_client, by_attr)
+                if trained is not None:
+                    trained[idx].copy_(flat)
+                else:
+                    agg.add(flat, idx, idxs_users, n_client, by_attr)
                 if has_buf:
                     agg_buf.add(eng.buffers_flat(), idx, idxs_users, n_client, None)
             if args.compat_sequential_optimizer and world > 1:
@@ -363,13 +421,20 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
             trainer.set_lr_epoch(sched_pos)
         # one all_reduce(SUM) of the flat buffer, shared_half_s under the reference's guard (utils/fed_utils.py:90),
         # EMA with the previous global: global_flat / global_buf are updated in place
-        agg.finish(epoch, args.round, grouped=by_attr is not None)
+        if trained is not None:
+            dist.all_reduce(trained, op=dist.ReduceOp.SUM)
+            for idx in idxs_users:
+                agg.add(trained[idx], idx, idxs_users, n_client, by_attr)
+            trained.zero_()
+        agg.finish(epoch, args.round, grouped=by_attr is not None, reduce=trained is None)
         if has_buf:
             agg_buf.finish(epoch, args.round, grouped=False)
         if dp is not None:                                           # every rank learns every client's norm (one sync per round)
             parts = [None] * world
             dist.all_gather_object(parts, agg.dp_stats)
             _dp_log(hist, dp, {c: v for part in parts for c, v in part.items()}, epoch, log if rank == 0 else (lambda *_: None))
+        if corr is not None:                                         # every rank: the round's new control variates, one all-reduce
+            _drift_log(hist, corr.finish_round(idxs_users), epoch, log if rank == 0 else (lambda *_: None))
         # personalisation needs every trained client's local prompts / lora_S on every rank that may test it:
         # exchange them (a few KB) with one more all-reduce of a zero-padded buffer
         keep = torch.zeros(users, flat.numel(), device=flat.device) if args.idxs_users_train else None
@@ -414,6 +479,8 @@ def run_fedotplora_ranks(trainer, args: FedArgs, attribute: Optional[str] = None
             log(f"round {epoch}: acc {hist['acc'][-1]:.3f} f1 {hist['f1'][-1]:.3f}"
                 + (f" auc {hist['auc'][-1]:.4f}" if hist["auc"] else ""))
     flat.copy_(global_flat)
+    if corr is not None:
+        eng.set_drift(None)
     if has_buf:
         eng.load_buffers_flat(global_buf)
         hist["global_buffers"] = global_buf.clone()

@@ -91,8 +91,14 @@ def build_parser() -> argparse.ArgumentParser:
     # accepted for script compatibility, unused on this path
     for flag, kw in (("--partition", dict(type=str, default="noniid-labeldir100")), ("--beta", dict(type=float, default=0.1)),
                      ("--iid", dict(default=False)), ("--useall", dict(default=False)), ("--num_shots", dict(type=int, default=2)),
-                     ("--mu", dict(type=float, default=0.5)), ("--logdir", dict(type=str, default="./logs/"))):
+                     ("--logdir", dict(type=str, default="./logs/"))):
         a(flag, **kw)
+    a("--drift", type=str, default="none", choices=["none", "fedprox", "scaffold"],
+      help="client-drift correction of every local step on the flat gradient buffer (fairfedmed_amd/drift.py): fedprox pulls "
+           "towards the round's starting point with weight --mu, scaffold adds control variates; an extension beyond the "
+           "reference's FedOTPLoRA branch, off by default")
+    a("--mu", type=float, default=0.5,
+      help="weight of the proximal term, read with --drift fedprox (the reference's flag and default); ignored otherwise")
     # build-specific
     a("--prec", type=str, default="bf16", choices=["bf16", "fp32", "amp", "fp16"],
       help="TRAINER.GLP_OT.PREC; the reference's 'fp16' runs as bf16 here, with a warning (trainer.resolve_precision)")
@@ -229,7 +235,8 @@ def fed_args(args):
                      idxs_users_test=args.idxs_users_test, shared_half_s=args.shared_half_s, local_s=args.lora_local_s,
                      seed=args.seed if args.seed > 0 else None,
                      compat_sequential_optimizer=args.compat_sequential_optimizer,
-                     dp_clip=args.dp_clip, dp_noise=args.dp_noise, dp_seed=args.dp_seed, dp_delta=args.dp_delta)
+                     dp_clip=args.dp_clip, dp_noise=args.dp_noise, dp_seed=args.dp_seed, dp_delta=args.dp_delta,
+                     drift=args.drift, mu=args.mu)
 
 
 def main(argv: Optional[List[str]] = None, log=print, cfg_hook=None):

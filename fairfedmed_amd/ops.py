@@ -1134,6 +1134,22 @@ def dp_philox(out: Tensor, seed: int, c0: int = 0, c1: int = 0, c2: int = 0, c3:
     _call("ffm_dp_philox", L.ptr(out), out.numel(), _seed64(seed), int(c0), int(c1), int(c2), int(c3), L.stream_ptr())
 
 
+def drift_correct(g: Tensor, p: Optional[Tensor] = None, anchor: Optional[Tensor] = None, mu: float = 0.0,
+                  c_diff: Optional[Tensor] = None, gsum: Optional[Tensor] = None, count: Optional[Tensor] = None,
+                  scale_state: Optional[Tensor] = None) -> None:
+    """Client-drift correction of the gradient in place (ffm_drift_correct): gsum += g and
+    count += 1 (the raw gradient), then g += mu * (p - anchor), then g += c_diff - each operand optional, every operation
+    rounded on its own.  With the fp16 gradient-scale state an overflowed step changes nothing."""
+    _dev(g, p, anchor, c_diff, gsum, count, scale_state)
+    n = g.numel()
+    for t in (p if anchor is not None else None, anchor, c_diff, gsum):
+        assert t is None or t.numel() == n
+    assert count is None or (count.dtype == torch.int64 and count.numel() == 1)
+    assert scale_state is None or scale_state.numel() == SCALE_STATE
+    _call("ffm_drift_correct", L.ptr(_f32(g)), L.ptr(_f32(p)), L.ptr(_f32(anchor)), float(mu), L.ptr(_f32(c_diff)),
+          L.ptr(_f32(gsum)), L.ptr(count), L.ptr(_f32(scale_state)), n, L.stream_ptr())
+
+
 def cast_from_f32(src: Tensor, dtype: torch.dtype) -> Tensor:
     _dev(src)
     dst = torch.empty(src.shape, dtype=dtype, device=src.device)

@@ -55,7 +55,7 @@ extern "C" {
 #define FFM_MAX_GROUPS 8
 
 /* library / build identification: returns FFM_ABI_VERSION */
-#define FFM_ABI_VERSION 14  /* still 14: ffm_gemm_skinny / ffm_attention_route (host queries beside ffm_gemm_tile_shape: does the skinny kernel serve this product, which attention kernels serve this length) are new symbols - purely additive; still 14: ffm_augment_boxes / ffm_crop_resize_u8 / ffm_augment_taps (train-time augmentation on the stored bytes, beside ffm_resize_u8, which is unchanged) are new symbols - purely additive; still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
+#define FFM_ABI_VERSION 14  /* still 14: ffm_drift_correct (client-drift correction of the local step - FedProx, SCAFFOLD - beside the optimizer entry points, which are unchanged) is a new symbol - purely additive; still 14: ffm_gemm_skinny / ffm_attention_route (host queries beside ffm_gemm_tile_shape: does the skinny kernel serve this product, which attention kernels serve this length) are new symbols - purely additive; still 14: ffm_augment_boxes / ffm_crop_resize_u8 / ffm_augment_taps (train-time augmentation on the stored bytes, beside ffm_resize_u8, which is unchanged) are new symbols - purely additive; still 14: ffm_eval_boot_ws_bytes / ffm_eval_boot_counts (bootstrap replicates of the evaluator's count table, beside ffm_eval_counts / ffm_eval_counts_sorted, which are unchanged) are new symbols - purely additive; still 14: ffm_dp_norm_ws_bytes / ffm_dp_norm / ffm_dp_privatise / ffm_dp_noise / ffm_dp_philox (client-level differential privacy at the round boundary, beside ffm_scale_by / ffm_scale_acc, which are unchanged) are new symbols - purely additive; still 14: ffm_resize_u8 (the native-size uint8 transport beside ffm_expand_u8, which is unchanged) is a new symbol - purely additive; still 14: ffm_ce_fair_loss (the fairness term of the loss beside ffm_ce_loss, which is unchanged) is a new symbol - purely additive; still 14: ffm_optim_step / ffm_optim_step_dev / ffm_optim_state_rows and ffm_optim_desc are new symbols beside the old ones - purely additive, no signature changed; 14: FFM_EPI_GELU_ONLY (the forward-only c_fc epilogue of the evaluation pass: the activation alone, in `c`), ffm_attention_fwd documents lse == NULL; 13: ffm_sgd_momentum_dev(repeats, state): the captured training step applies `repeats` updates and is gated by the fp16 gradient scale like ffm_sgd_momentum_gated; 12: FFM_EPI_LNB_STAT / FFM_EPI_LNB_APPLY (LayerNorm backward folded into the dX products of the MLP; ffm_gemm_args.lnb_*), ffm_gemm_args.sk_part + ffm_gemm_splitk_floats (text-tower products split over K), ffm_scale_acc, ffm_loss_scale / ffm_unscale_check / ffm_sgd_momentum_gated (device-resident fp16 gradient scale); 11: FFM_EPI_BNBWD (ffm_gemm_args.bn_x / bn_mask / bn_mean / bn_rstd / bn_gout), ffm_bn_bwd part_rows; 10: ffm_lora_down_blocks is exact again, ffm_lora_down_blocks_max sizes buffers, ffm_slice_wgrad_blocks (wpart rows, no longer ffm_slice_blocks); 9: FFM_EPI_LGRAD (ffm_gemm_args.lg_v / lg_part_c / lg_part_a), ffm_gemm_lgrad_rows; 8: FFM_F16 (IEEE-half twins of every 16-bit kernel behind the same entry points), ffm_scale_check; 7: ffm_text_embed / ffm_text_tail_fwd / ffm_text_tail_bwd / ffm_text_ctx_grad; 6: FFM_F32_X3, ffm_gemm_args.lw_wide / LayerNorm folding fields, ffm_pack_desc.dst_wide, ffm_eval_counts_sorted, ffm_gemm_tiles_n, colstat_part / ffm_bn_fwd part_rows; 5: ffm_sgd_momentum_n; 4: ffm_reduce_partials_multi launch width (max_n), new entry points (conv3x3, eval counts, uint8) */
 int ffm_abi_version(void);
 
 /* The value in use for the diagnostic switch whose environment variable is `name` ("FFM_PANEL", "FFM_ATTN", ...: the rows
@@ -872,6 +872,25 @@ int ffm_dp_privatise(const float* theta, const float* g, const float* w, float* 
  * (c0 + (j >> 2), c1, c2, c3), key (low, high word of seed)); the counter words are taken modulo 2^32. */
 int ffm_dp_noise(float* out, int64_t n, float sigma, int64_t seed, int round, int client, void* stream);
 int ffm_dp_philox(int32_t* out, int64_t n, int64_t seed, int64_t c0, int64_t c1, int64_t c2, int64_t c3, void* stream);
+
+/*
+ * Client-drift correction in the local step (an extension: the reference's FedOTPLoRA branch runs plain
+ * FedAvg).  One elementwise pass over the flat gradient buffer between the backward pass and the optimizer launch; every
+ * operand but g may be NULL, every line is one rounded fp32 operation (no contraction), in this order, for each i < n:
+ *     raw = g[i]
+ *     gsum:    gsum[i] = gsum[i] + raw          (SCAFFOLD: the running sum of the raw gradients of this client-round)
+ *     anchor:  d = p[i] - anchor[i];  t = mu * d;  x = raw + t      (FedProx: the gradient of (mu / 2) |p - anchor|^2)
+ *     c_diff:  x = x + c_diff[i]                (SCAFFOLD: c - c_i)
+ *     g[i] = x
+ * and, with count, *count += 1 (one thread).  scale_state (may be NULL) is the fp16 gradient-scale state of ffm_loss_scale:
+ * when ok == 0 the launch changes nothing - not g, not gsum, not count - as the gated optimizer launch behind it changes
+ * nothing, so a non-finite gradient never enters the running sum.  16-byte loads and stores when every given pointer is
+ * 16-byte aligned, element by element otherwise - the same values.  FFM_EINVAL (nothing launched): g NULL, n <= 0, mu not
+ * finite, anchor without p, mu != 0 without anchor, gsum without count or count without gsum, or no operand at all;
+ * FFM_EUNSUP: n > 2^34 (the limit of ffm_dp_norm).
+ */
+int ffm_drift_correct(float* g, const float* p, const float* anchor, float mu, const float* c_diff, float* gsum,
+                      int64_t* count, const float* scale_state, int64_t n, void* stream);
 
 /* dtype conversion helpers (weight preparation at load time). */
 int ffm_cast_f32_to(const float* src, void* dst, int64_t n, int dtype, void* stream);
